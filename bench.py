@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- NMF iterations/sec on MI355X for BASELINE.json's headline configuration.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg2|cfg5] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg2|cfg5] [--dump-outputs DIR] [--full [--no-cpu]]
 
 A "step" is ONE solver iteration of proxmin_amd's nmf() hot path on synthetic data already resident
 in HBM: the fused residual-gradient pass over Y (6MNK flop; 8MNK and two passes for bsdmm) plus the
@@ -11,8 +11,15 @@ the columns of S.  With --gpus N > 1 (launched by torch.distributed.run, one ran
 of Y and A are sharded over the ranks and gS is all-reduced once per iteration (strong scaling).
 
 Prints ONE JSON line (rank 0).  `roofline` describes the dominant kernel (K1, k_grad_f32) from HIP
-events recorded on its launch stream inside the timed region; `cpu_baseline` is the NumPy oracle
-(a validated restatement of the reference) timed on this box's host cores on a bounded sample.
+events recorded on its launch stream inside the timed region.  A plain run measures the headline
+alone: set-up, warm-up, the timed steps, the line.  `--full` adds the side measurements: the box's
+measured peaks and K1's energy floor, the same workload in the other arithmetic modes, the other
+BASELINE configurations, the nmf() calls, the fp64 leg and `cpu_baseline`, the NumPy oracle (a
+validated restatement of the reference) timed on this box's host cores.
+
+`--dump-outputs DIR` writes what the timed path computed, the factors A and S after its last step,
+as DIR/A.npy and DIR/S.npy (float32; a fixed, seeded sample of entries where they exceed 64 MB).
+The inputs are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -412,20 +419,52 @@ def other_configs(Y3, local):
     return res
 
 
-def main():
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write each array as path/<name>.npy in float32 / float64.  When they exceed `limit` bytes together, each is replaced by a
+    sample of its entries (flat indices drawn from np.random.default_rng(0), sorted; the same in every run) and the indices are
+    written beside it as <name>_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    frac = limit * 0.99 / sum(a.size * (a.itemsize + 8) for a in arrays.values())      # (the float64 index files count as well)
+    for name, a in arrays.items():
+        if total > limit:
+            n = max(1, int(a.size * frac))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False)).astype(np.float64)
+            np.save(os.path.join(path, name + "_index.npy"), idx)
+            a = a.reshape(-1)[idx.astype(np.int64)]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu", action="store_true", help="the headline alone: no CPU baseline and none of the side legs (peaks, other configurations, nmf() leg)")
-    ap.add_argument("--skip-cpu-baseline", action="store_true", help="everything but the CPU leg (tuning: A/B runs that want other_configs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: measured peaks and K1's energy floor, the other arithmetic modes, the other configurations, the nmf() calls, "
+                         "the fp64 leg (cfg3) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the factors A and S after the last timed step as DIR/A.npy and DIR/S.npy (float32; one GPU)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: the headline alone, no CPU baseline and none of the side legs (peaks, other configurations, nmf() leg)")
+    ap.add_argument("--skip-cpu-baseline", action="store_true", help="with --full: everything but the CPU leg (tuning: A/B runs that want other_configs)")
     ap.add_argument("--rows", type=int, default=0, help="override M (debug)")
     ap.add_argument("--mode", default=None, choices=["f32", "bf16x3", "f16x2", "f16x2r"],
                     help="contraction arithmetic: f16x2r = fp16 split MFMA in exact fp32's error class (default for cfg3 / cfg4 / cfg5: the headline), "
                          "f16x2 = two-term fp16 split MFMA (faster to issue at K = 32 only; 2-4 x fp32's out-of-tolerance entries), "
                          "bf16x3 = three-term bf16 split MFMA, f32 = exact fp32 MFMA (default for cfg2, which BASELINE quotes in fp32)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("PMX_FORCE_SHARDED")):
+        ap.error("--dump-outputs: single-GPU runs only")
+    return args
+
+
+def main():
+    args = parse_args()
     if args.mode is None:
         # [r6] the LIBRARY'S default arithmetic (proxmin_amd.engine.LIBRARY_DEFAULT_MODE = f16x2r): the headline needs no --mode; cfg2 is the one
         # configuration BASELINE quotes in fp32, so its own line runs exact fp32 (its f16x2r number is in other_configs)
@@ -470,11 +509,11 @@ def main():
     Y, A0, S0 = make_problem_device(M, N, K, unity, 1234, device)
     torch.cuda.synchronize()
 
-    # [r6] Everything that is NOT the headline runs FIRST: the box's measured peaks and K1's energy floor, the same workload in the
-    # other arithmetic modes, the other BASELINE configurations, one nmf() call through the public entry point.  The timed region of the headline
-    # (20 steps = 8 ms with the driver's flags: inside one DVFS time constant) then starts on a package that has been busy for seconds.
+    # [r6] With --full, everything that is NOT the headline runs FIRST: the box's measured peaks and K1's energy floor, the same
+    # workload in the other arithmetic modes, the other BASELINE configurations, one nmf() call through the public entry point.  The timed region of
+    # the headline (20 steps = 8 ms with the driver's flags: inside one DVFS time constant) then starts on a package that has been busy for seconds.
     side = {}
-    full = args.config == "cfg3" and not args.rows and not args.no_cpu
+    full = args.full and args.config == "cfg3" and not args.rows and not args.no_cpu
     if full:
         side["measured"] = measured_on_this_box(local)
         for key, mode, warm_s, steps_s, note in (("value_f32_mode", "f32", 25, 20, "same workload in exact fp32 (mode f32: %s)"),
@@ -534,6 +573,9 @@ def main():
     dev.set_timing(False)
     assert res.iterations == args.steps, "chain ended early (%d of %d iterations)" % (res.iterations, args.steps)
     sub_timed = [(int(res.sub_iterations[j]) - sub_seen[j]) / float(args.steps) for j in range(2)]
+    if args.dump_outputs:
+        A_out, S_out = dev.get_factors()
+        dump_outputs(args.dump_outputs, {"A": A_out, "S": S_out})
 
     dt = t1 - t0
     flop_per_it = (8.0 if backend == "bsdmm" else 6.0) * M * N * K
@@ -584,7 +626,7 @@ def main():
     out.update({k: v for k, v in side.items() if k != "measured"})
     if meas:
         out["measured_on_this_box"] = meas
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         dev.close()
         Yh = Y.cpu().numpy()
         del Y

@@ -9,7 +9,7 @@ cd $R
 cp gpurun_out/k1_traffic.json profiles/k1_traffic.json
 PMC=1 ./scratch/prof_r2.sh r02_d > $O/prof.log 2>&1
 export MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python bench.py --steps 20 --warmup 5 --no-cpu > $O/bench_20_5.json 2>/dev/null
 python bench.py --mode f32 --no-cpu > $O/bench_f32.json 2>/dev/null
 python bench.py --mode bf16x3 --no-cpu > $O/bench_bf16x3.json 2>/dev/null

@@ -17,7 +17,7 @@ python -c 'import __graft_entry__ as g; g.smoke(); print("smoke ok")' > $O/smoke
 cp gpurun_out/k1_traffic.json profiles/k1_traffic.json
 cp gpurun_out/k1_traffic.json $O/k1_traffic.json
 PMC=1 ./scratch/prof_r2.sh $TAG > $O/prof.log 2>&1
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python bench.py --steps 20 --warmup 5 --no-cpu > $O/bench_20_5.json 2>/dev/null
 python bench.py --mode f32 --no-cpu > $O/bench_f32.json 2>/dev/null
 python bench.py --mode f16x2 --no-cpu > $O/bench_f16x2.json 2>/dev/null

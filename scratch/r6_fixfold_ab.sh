@@ -30,7 +30,7 @@ PMX_FIX_FOLD_IN_K1=0 python /tmp/fix_hash.py > $O/hash_0.txt 2>/dev/null
 if diff -q $O/hash_1.txt $O/hash_0.txt > /dev/null; then echo "factors IDENTICAL with and without the correction's fold in K1 ($(wc -l < $O/hash_1.txt) runs)"; cat $O/hash_1.txt; else echo "DIFFERENT:"; diff $O/hash_1.txt $O/hash_0.txt; fi
 for rep in 1 2 3; do
 for F in 1 0; do
-  PMX_FIX_FOLD_IN_K1=$F python bench.py --skip-cpu-baseline > $O/bench_fold${F}_$rep.json 2> /dev/null
+  PMX_FIX_FOLD_IN_K1=$F python bench.py --full --skip-cpu-baseline > $O/bench_fold${F}_$rep.json 2> /dev/null
   grep '^{' $O/bench_fold${F}_$rep.json | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())

@@ -7,7 +7,7 @@ mkdir -p $O
 cd $R
 for rep in 1 2; do
 for P in 0 1 2 3 -1; do
-  PMX_K1_PRIO=$P python bench.py --skip-cpu-baseline > $O/bench_prio${P}_$rep.json 2> /dev/null
+  PMX_K1_PRIO=$P python bench.py --full --skip-cpu-baseline > $O/bench_prio${P}_$rep.json 2> /dev/null
   grep '^{' $O/bench_prio${P}_$rep.json | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())

@@ -29,7 +29,7 @@ if diff -q $O/hash_new.txt $O/hash_base.txt > /dev/null; then echo "factors IDEN
 for rep in 1 2 3; do
 for F in new base; do
   if [ $F = base ]; then export PMX_LIB=$PWD/scratch/libpmx_base.so; else unset PMX_LIB; fi
-  python bench.py --skip-cpu-baseline --steps 20 --warmup 3 > $O/bench_${F}_$rep.json 2> /dev/null
+  python bench.py --full --skip-cpu-baseline --steps 20 --warmup 3 > $O/bench_${F}_$rep.json 2> /dev/null
   grep '^{' $O/bench_${F}_$rep.json | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())

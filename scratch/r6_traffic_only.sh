@@ -10,8 +10,8 @@ cd $GRAFT_REPO_ROOT; O=gpurun_out/r06_y; mkdir -p $O
 ./scratch/measure_traffic.sh cfg4 f16x2r 8192 >> $O/traffic.log 2>&1
 cp gpurun_out/k1_traffic.json profiles/k1_traffic.json
 cp gpurun_out/k1_traffic.json $O/k1_traffic.json
-python bench.py --steps 20 --warmup 5 > $O/bench_20_5.json 2> $O/bench_20_5.err
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_20_5.json 2> $O/bench_20_5.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 for f in bench_20_5 bench_default; do grep '^{' $O/$f.json | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())

@@ -71,3 +71,32 @@ def test_roofline_entry_arithmetic():
     assert abs(r["achieved"] - M * N * 4 / 0.3524e-3 / 1e9) < 1e-6 and abs(r["frac"] - r["achieved"] / 8000.0) < 1e-12
     r32 = bench.roofline_entry("f32", M, N, K, 6.0 * M * N * K, 0.8167, 25, 0.9, "k_grad_f32_pc")
     assert r32["bound"] == "mfma" and r32["unit"] == "TFLOP/s" and abs(r32["frac"] - 6.0 * M * N * K / 0.8167e-3 / 1e12 / bench.PEAK_F32_MFMA_TFLOPS) < 1e-9
+
+
+def test_plain_run_is_the_headline_alone_and_full_is_opt_in():
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.steps == 7 and a.warmup == 3 and not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--gpus", "2", "--dump-outputs", "out"])        # the factors of one rank are not what a caller receives
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    import numpy as np
+    rng = np.random.default_rng(5)
+    A = rng.random((300, 8), dtype=np.float32)
+    S = rng.random((8, 500))                                                # float64 stays float64
+    bench.dump_outputs(str(tmp_path / "all"), {"A": A, "S": S})
+    assert sorted(os.listdir(tmp_path / "all")) == ["A.npy", "S.npy"]
+    assert np.array_equal(np.load(tmp_path / "all" / "A.npy"), A) and np.load(tmp_path / "all" / "S.npy").dtype == np.float64
+    # over the limit: the same seeded sample of entries in every run, with its flat indices
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"A": A, "S": S}, limit=20000)
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["A.npy", "A_index.npy", "S.npy", "S_index.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 20000 + 4 * 128     # (+ the .npy headers)
+    for f in ("A.npy", "A_index.npy", "S.npy", "S_index.npy"):
+        assert np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f))
+    idx = np.load(tmp_path / "s1" / "A_index.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "s1" / "A.npy"), A.reshape(-1)[idx])
