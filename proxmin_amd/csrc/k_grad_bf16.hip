@@ -1429,8 +1429,8 @@ GradPlan grad_plan_bf16(int64_t M, int64_t N, int64_t K) {
     const int64_t panels = (M + BG_BM - 1) / BG_BM;
     p.gridY = (int)((N + (int64_t)BG_CB * BG_BN - 1) / ((int64_t)BG_CB * BG_BN));
     // one resident workgroup per CU for the 8-wave variants: a single round of 256 measured 1-12 % faster than two of
-    // 512 (fewer prologues / accumulator flushes, half the gSt slabs); PMX_K1_WGS overrides (tuning)
-    const int wantWG = getenv("PMX_K1_WGS") ? atoi(getenv("PMX_K1_WGS")) : (p.variant >= 4 && K == 64 ? 256 : 512);
+    // 512 (fewer prologues / accumulator flushes, half the gSt slabs)
+    const int wantWG = p.variant >= 4 && K == 64 ? 256 : 512;
     plan_row_regions(panels, p.gridY, wantWG, &p.RP, &p.gridX);
     p.nSlabA = p.gridY * splitA;
     p.nSlabS = p.gridX * splitS;
@@ -1468,40 +1468,17 @@ static hipError_t grad_launch_bf16_t(const GradPlan& p, const GradBfArgs& a, hip
     return hipGetLastError();
 }
 
-// true when the split-bf16 path of this shape accepts a weighted likelihood (k_grad_bf16_v7<.., HASW = true>)
-bool grad_bf16_takes_weights(const GradPlan& p, int64_t M, int64_t N, int64_t K);
-// true when the launch below will take the variant that reads A and St as fp32 (no presplit pass needed)
+// true when the split-bf16 path of this shape reads A and St as fp32 (k_grad_bf16_v7, and k_grad_f16_v8 in mode f16x2: no presplit pass,
+// weights taken); anything else runs k_grad_bf16 / k_grad_bf16_pipe on presplit terms
 bool grad_bf16_reads_fp32(const GradPlan& p, int64_t M, int64_t N, int64_t K) {
     return p.variant >= 7 && p.KP == 64 && K == 64 && (M % V4_BM) == 0 && (N % (V5_NB * V5_BN)) == 0;
 }
-bool grad_bf16_takes_weights(const GradPlan& p, int64_t M, int64_t N, int64_t K) {
-    return grad_bf16_reads_fp32(p, M, N, K);
-}
-// took_f16 (optional): whether the two-term fp16 kernel is what runs -- a context in mode f16x2 drops to the split-bf16 kernel of
-// the same frame at launch time when Y (or W) cannot be fetched eight bytes at a time (odd pitch, misaligned base, ldW != ldY)
-hipError_t grad_launch_bf16(const GradPlan& p, const GradBfArgs& a_, const float* A, const float* St, hipStream_t stream, int* nloss, bool* took_f16 = nullptr) {
+// k_grad_bf16 / k_grad_bf16_pipe (the shapes grad_bf16_reads_fp32 does not take)
+hipError_t grad_launch_bf16(const GradPlan& p, const GradBfArgs& a_, hipStream_t stream) {
     GradBfArgs a = a_;
     a.gridX = p.gridX;
     a.gridY = p.gridY;
-    *nloss = p.gridX * p.gridY;
     const int variant = p.variant;
-    if (grad_bf16_reads_fp32(p, a.M, a.N, a.K)) {
-        GradV4Args g{};
-        g.Y = a.Y; g.ldY = a.ldY; g.A = A; g.St = St;
-        g.slabA = a.slabA; g.slabS = a.slabS; g.lossPart = a.lossPart; g.status = a.status;
-        g.M = a.M; g.N = a.N; g.RP = a.RP; g.doA = a.doA; g.doS = a.doS;
-        g.gridX = p.gridX; g.gridY = p.gridY; g.prof = a.prof;
-        g.W = a.W; g.ldW = a.ldW;
-        g.absmax = a.absmax; g.ymax = a.ymax; g.wmax = a.wmax;
-        g.chainL = a.chainL; g.chainFlags = a.chainFlags; g.chainBase = a.chainBase; g.wstatus = a.wstatus; g.chainInject = a.chainInject; g.rangeRatio = a.rangeRatio; g.r3 = a.r3; g.consPrio = a.consPrio;
-        // fp16 two-term mode; its producers fetch Y (and W) eight bytes at a time: even pitch, 8-byte-aligned base (anything
-        // else runs the split-bf16 kernel of the same frame below)
-        const bool pairs_ok = (a.ldY % 2) == 0 && (((uintptr_t)a.Y) & 7) == 0 && (a.W == nullptr || (a.ldW == a.ldY && (((uintptr_t)a.W) & 7) == 0));   // (the weights share Y's per-lane offsets)
-        const bool f16 = a.absmax != nullptr && pairs_ok;
-        if (took_f16) *took_f16 = f16;
-        if (f16) return grad_launch_f16_v8(g, stream);
-        return grad_launch_bf16_v7(g, stream);   // plain loads: any row pitch
-    }
     if (a.W != nullptr) return hipErrorInvalidValue;
     // Whole blocks with 16-byte-aligned rows take an LDS-DMA variant; anything else the guarded kernel.
     const bool aligned = (a.ldY % 4) == 0 && (((uintptr_t)a.Y) & 15) == 0;

@@ -124,7 +124,7 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_k32(GradV4Args a) {
     }
 
     if (producer) {
-        k1_set_priority(-a.consPrio);      // (PMX_K1_PRIO < 0: the producers instead -- A/B only)
+        k1_set_priority(-a.consPrio);      // (a negative level: the producers instead -- no launch asks for it)
         // ================================ producers: P = A S and R ================================================
         f32x16 p0, p1;
         f32x16 q0, q1;                       // R3: the small products' accumulators
@@ -433,10 +433,9 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_k32(GradV4Args a) {
 }
 
 // host side -----------------------------------------------------------------------------------------
-// shapes the kernel takes (PMX_K1_K32=0: off -- the split-bf16 kernels of rounds 1-3 instead; tuning A/B)
+// shapes the kernel takes
 bool grad_f16_k32_applies(int64_t M, int64_t N, int64_t K) {
-    if (K != 32 || M % V5_BM != 0 || N % (V5_NB * V5_BN) != 0) return false;
-    return !(getenv("PMX_K1_K32") && atoi(getenv("PMX_K1_K32")) == 0);
+    return K == 32 && M % V5_BM == 0 && N % (V5_NB * V5_BN) == 0;
 }
 GradPlan grad_plan_f16_k32(int64_t M, int64_t N) {
     GradPlan p{};
@@ -444,8 +443,7 @@ GradPlan grad_plan_f16_k32(int64_t M, int64_t N) {
     p.BN = V5_BN;
     const int64_t panels = M / V5_BM;
     p.gridY = (int)(N / (V5_NB * V5_BN));
-    const int wantWG = getenv("PMX_K1_WGS") ? atoi(getenv("PMX_K1_WGS")) : 256;   // one resident workgroup per CU
-    plan_row_regions(panels, p.gridY, wantWG, &p.RP, &p.gridX);
+    plan_row_regions(panels, p.gridY, 256, &p.RP, &p.gridX);    // one resident workgroup per CU
     p.nSlabA = p.gridY;
     p.nSlabS = p.gridX;
     p.ldsBytes = V8_LDS_BYTES;
@@ -459,8 +457,9 @@ static hipError_t grad_launch_f16_k32_t(const GradV4Args& a, hipStream_t stream)
     hipLaunchKernelGGL((k_grad_f16_k32<LOSS, R3>), dim3(a.gridX * a.gridY), dim3(V5_THREADS), lds, stream, a);
     return hipGetLastError();
 }
-hipError_t grad_launch_f16_k32(const GradV4Args& a, hipStream_t stream) {
-    if (a.r3) return (!(a.doA & 1) && !a.doS) ? grad_launch_f16_k32_t<true, true>(a, stream) : grad_launch_f16_k32_t<false, true>(a, stream);
+// inst (k1_instance): K1_R3 or K1_PLAIN
+hipError_t grad_launch_f16_k32(const GradV4Args& a, K1Inst inst, hipStream_t stream) {
+    if (inst == K1_R3) return (!(a.doA & 1) && !a.doS) ? grad_launch_f16_k32_t<true, true>(a, stream) : grad_launch_f16_k32_t<false, true>(a, stream);
     if (!(a.doA & 1) && !a.doS) return grad_launch_f16_k32_t<true>(a, stream);      // the loss-only pass (pmx_loglike, the line search)
     return grad_launch_f16_k32_t<false>(a, stream);
 }

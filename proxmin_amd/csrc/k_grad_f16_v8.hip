@@ -6,9 +6,6 @@
 // ------------------------------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-#ifndef PMX_CHAIN_PF
-#define PMX_CHAIN_PF 4       // pieces of a chain's previous sum in flight (k_grad_f16_v8<.., RS>'s gA waves): all four requested behind the arrival check (profiles/r06_q_chain_prefetch_ab.txt); 0 = rounds 2-5
-#endif
 constexpr int V8_NPART = 256;                // partial maxima per factor
 
 __device__ __forceinline__ void v8_split2(const float4& x, float sc, f16x4& h, f16x4& l) {
@@ -70,7 +67,7 @@ __device__ __forceinline__ bool f16_range_fault(float boundP, float ymax, float 
 
 // [r6] static priority for one role of the workgroup (MI355X_MICROARCH.md "two waves per SIMD", item 4): each SIMD hosts one producer and one consumer wave;
 // the consumers (24 MFMAs + their LDS operand reads per slot) are the pole, the producers wait at the barrier.  Arbitration is by priority, then age --
-// and the consumers are the YOUNGER half.  One s_setprio for the launch, no per-slot flips.  Level from the launch arguments (PMX_K1_PRIO: A/B).
+// and the consumers are the YOUNGER half.  One s_setprio for the launch, no per-slot flips.  Level from the launch arguments (k1_prio_for).
 __device__ __forceinline__ void k1_set_priority(int level) {
     if (level == 1) __builtin_amdgcn_s_setprio(1);
     else if (level == 2) __builtin_amdgcn_s_setprio(2);
@@ -289,7 +286,7 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
     }
 
     if (producer) {
-        k1_set_priority(-a.consPrio);      // (PMX_K1_PRIO < 0: the producers instead -- A/B only)
+        k1_set_priority(-a.consPrio);      // (a negative level: the producers instead -- no launch asks for it)
         // ================================ producers: GEMM1 and R =================================================
         f32x16 p0, p1;
         f32x16 q0, q1;                       // R3: the small products' accumulators (see the kernel's header)
@@ -619,11 +616,9 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
             // [r6] The previous sum of the panel arrives in four pieces (accumulator registers 4 p .. 4 p + 3 of all four tiles), piece p added behind the MFMAs of
             // slot 4 + p.  Requested in FRONT of those MFMAs (rounds 2-5) a piece had 24 MFMAs = ~0.4 us to arrive -- less than a round trip to the L2 under the
             // stream of Y, and the consumers' pole waited for the rest in four slots of every panel (the 6 % the chains cost inside K1, profiles/r05_d_chain_length.txt).
-            // Now the pieces are requested PF at a time as soon as the arrival word has been seen (behind slot 3's MFMAs) and piece p + PF behind the add of piece p:
-            // a whole slot (barrier, operand reads, MFMAs) or more per round trip.  The adds stand where they stood: the same sums in the same order, bit for bit.
-            constexpr int PF = PMX_CHAIN_PF;          // pieces in flight (buffers of 16 registers): 0 = the old placement
-            static_assert(PF >= 0 && PF <= 4, "");
-            float pv[PF > 0 ? PF : 1][2][2][4];
+            // Now all four pieces are requested as soon as the arrival word has been seen (behind slot 3's MFMAs): a whole slot (barrier, operand reads, MFMAs)
+            // or more per round trip (profiles/r06_q_chain_prefetch_ab.txt).  The adds stand where they stood: the same sums in the same order, bit for bit.
+            float pv[4][2][2][4];                     // the four pieces in flight (buffers of 16 registers)
             auto fetch_piece = [&](int prow_, auto p_c) {
                 constexpr int p = decltype(p_c)::value;
 #pragma unroll
@@ -631,8 +626,8 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
                     const float* pb = gA_tile(prow_, rt) + (8 * (p & 1) + 16 * (p >> 1)) * K;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        pv[PF > 0 ? p % PF : 0][rt][0][q] = __builtin_bit_cast(float, __hip_atomic_load((const unsigned*)(pb + q * K), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                        pv[PF > 0 ? p % PF : 0][rt][1][q] = __builtin_bit_cast(float, __hip_atomic_load((const unsigned*)(pb + q * K + 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                        pv[p][rt][0][q] = __builtin_bit_cast(float, __hip_atomic_load((const unsigned*)(pb + q * K), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                        pv[p][rt][1][q] = __builtin_bit_cast(float, __hip_atomic_load((const unsigned*)(pb + q * K + 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
                     }
                 }
             };
@@ -649,14 +644,6 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
                     }
                     if constexpr (CHAIN) {
                         if (cb == 3) link.look();
-                        if constexpr (PF == 0) {
-                            if (cb >= 4 && link.cadd) {
-                                if (cb == 4) fetch_piece(prow, std::integral_constant<int, 0>{});
-                                if (cb == 5) fetch_piece(prow, std::integral_constant<int, 1>{});
-                                if (cb == 6) fetch_piece(prow, std::integral_constant<int, 2>{});
-                                if (cb == 7) fetch_piece(prow, std::integral_constant<int, 3>{});
-                            }
-                        }
                     }
                     {
                         const unsigned char* Rb = smem + OFF_R + ((s - 2) & 1) * V5_R_BYTES;
@@ -684,29 +671,21 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
                     if constexpr (CHAIN) {
                         if (cb == 3) {
                             link.wait();
-                            if constexpr (PF > 0) {
-                                if (link.cadd) {
-                                    fetch_piece(prow, std::integral_constant<int, 0>{});
-                                    if constexpr (PF > 1) fetch_piece(prow, std::integral_constant<int, 1>{});
-                                    if constexpr (PF > 2) fetch_piece(prow, std::integral_constant<int, 2>{});
-                                    if constexpr (PF > 3) fetch_piece(prow, std::integral_constant<int, 3>{});
-                                }
+                            if (link.cadd) {
+                                fetch_piece(prow, std::integral_constant<int, 0>{});
+                                fetch_piece(prow, std::integral_constant<int, 1>{});
+                                fetch_piece(prow, std::integral_constant<int, 2>{});
+                                fetch_piece(prow, std::integral_constant<int, 3>{});
                             }
                         }
                         if (cb >= 4 && link.cadd) {
-                            const int b_ = PF > 0 ? (cb - 4) % PF : 0;
 #pragma unroll
                             for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
                                 for (int q = 0; q < 4; ++q) {
-                                    accA[rt][0][4 * (cb - 4) + q] += pv[b_][rt][0][q] * invUnA;
-                                    accA[rt][1][4 * (cb - 4) + q] += pv[b_][rt][1][q] * invUnA;
+                                    accA[rt][0][4 * (cb - 4) + q] += pv[cb - 4][rt][0][q] * invUnA;
+                                    accA[rt][1][4 * (cb - 4) + q] += pv[cb - 4][rt][1][q] * invUnA;
                                 }
-                            if constexpr (PF > 0 && PF < 4) {          // the buffer is free: the piece PF places on
-                                if (cb - 4 + PF == 1) fetch_piece(prow, std::integral_constant<int, 1>{});
-                                if (cb - 4 + PF == 2) fetch_piece(prow, std::integral_constant<int, 2>{});
-                                if (cb - 4 + PF == 3) fetch_piece(prow, std::integral_constant<int, 3>{});
-                            }
                         }
                     }
                     if (cb + 1 == NCB) {
@@ -1017,16 +996,17 @@ static hipError_t grad_launch_f16_v8_t(const GradV4Args& a, hipStream_t stream) 
     hipLaunchKernelGGL((k_grad_f16_v8<PROF, HASW, CHAIN, LOSS, R3, HH, RS, ONLYS>), dim3(a.gridX * a.gridY), dim3(V5_THREADS), lds, stream, a);
     return hipGetLastError();
 }
-static hipError_t grad_launch_f16_v8(const GradV4Args& a, hipStream_t stream) {
-    // r3 == 2 [r5]: the high x high residual whose missing terms arrive as a correction slab (<HH>; gradient passes only -- the loss-only pass
-    // has nowhere to put a correction and runs the third terms' instance)
-    if (a.r3 == 2 && a.W == nullptr && (a.doA & 1) && a.doS && !a.prof && !(getenv("PMX_K1_ROLE_SPLIT") && atoi(getenv("PMX_K1_ROLE_SPLIT")) == 0))   // <RS>: both gradients wanted (PMX_K1_ROLE_SPLIT=0: A/B)
-        return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, false, true, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, false, true, true>(a, stream);
-    if (a.r3 == 2 && a.W == nullptr && !(a.doA & 1) && a.doS && !(getenv("PMX_K1_ROLE_SPLIT") && atoi(getenv("PMX_K1_ROLE_SPLIT")) == 0))      // <ONLYS>: gSt alone (same A/B switch)
-        return grad_launch_f16_v8_t<false, false, false, false, false, true, false, true>(a, stream);
-    if (a.r3 == 2 && a.W == nullptr && ((a.doA & 1) || a.doS))
+// inst (k1_instance): K1_HH, K1_R3 or K1_PLAIN
+static hipError_t grad_launch_f16_v8(const GradV4Args& a, K1Inst inst, hipStream_t stream) {
+    if (inst == K1_HH) {             // [r5] the high x high residual whose missing terms arrive as a correction slab
+        const bool split = !(getenv("PMX_K1_ROLE_SPLIT") && atoi(getenv("PMX_K1_ROLE_SPLIT")) == 0);     // (PMX_K1_ROLE_SPLIT=0: A/B)
+        if (split && (a.doA & 1) && a.doS && !a.prof)   // <RS>: both gradients wanted
+            return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, false, true, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, false, true, true>(a, stream);
+        if (split && !(a.doA & 1) && a.doS)             // <ONLYS>: gSt alone
+            return grad_launch_f16_v8_t<false, false, false, false, false, true, false, true>(a, stream);
         return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, false, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, false, true>(a, stream);
-    if (a.r3 && a.W == nullptr) {    // R3: the residual to fp32's class (unweighted instances; a weighted context keeps two terms)
+    }
+    if (inst == K1_R3) {             // the residual to fp32's class
         if (!(a.doA & 1) && !a.doS) return grad_launch_f16_v8_t<false, false, false, true, true>(a, stream);
         return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, true>(a, stream);
     }

@@ -404,10 +404,9 @@ __global__ __launch_bounds__(512, 2) void k_grad_f32_pc(GradArgs a, int gridX, i
 }
 
 // host side -----------------------------------------------------------------------------------------
-// shapes the kernel takes (PMX_K1_F32PC=0: off, k_grad_f32 instead -- tuning A/B)
+// shapes the kernel takes
 bool grad_f32pc_applies(int64_t M, int64_t N, int64_t K) {
-    if ((K != 32 && K != 64) || M % 128 != 0 || N % 256 != 0) return false;
-    return !(getenv("PMX_K1_F32PC") && atoi(getenv("PMX_K1_F32PC")) == 0);
+    return (K == 32 || K == 64) && M % 128 == 0 && N % 256 == 0;
 }
 GradPlan grad_plan_f32pc(int64_t M, int64_t N, int64_t K) {
     GradPlan p{};
@@ -415,8 +414,7 @@ GradPlan grad_plan_f32pc(int64_t M, int64_t N, int64_t K) {
     p.BN = 32;
     const int64_t panels = M / 128;
     p.gridY = (int)(N / 256);
-    const int wantWG = getenv("PMX_K1_WGS") ? atoi(getenv("PMX_K1_WGS")) : 256;   // one resident workgroup per CU
-    plan_row_regions(panels, p.gridY, wantWG, &p.RP, &p.gridX);
+    plan_row_regions(panels, p.gridY, 256, &p.RP, &p.gridX);    // one resident workgroup per CU
     p.nSlabA = p.gridY;
     p.nSlabS = p.gridX;                                  // ([r4] the row parts are merged inside the launch)
     p.ldsBytes = sizeof(float) * (K == 64 ? F32pcCfg<64>::LDS_FLOATS : F32pcCfg<32>::LDS_FLOATS);

@@ -25,12 +25,9 @@
 // carrying the writer's XCC_ID, sc1 fetch-and-add in the consumers' registers, fault -> slabs), re-timed for a panel of
 // four blocks: arrival looked at in the panel's second block, the previous sum fetched in two halves of 32 registers during
 // the third and fourth, published one slot into the next panel.  A member's panels are rotated by `chainStride` panels per
-// place in the chain (2 where the region has the panels for it: the predecessor's sum is then a whole panel-time old when it
-// is asked for).  gA: one slab per CHAIN (N / 128 / chainL of them) instead of one per column region.
+// place in the chain (the host passes 1: 2, where the predecessor's sum is a whole panel-time old when it is asked for, measured
+// slower -- profiles/r04_a_k128_chain_ab.txt).  gA: one slab per CHAIN (N / 128 / chainL of them) instead of one per column region.
 // ------------------------------------------------------------------------------------------------
-#ifndef PMX_CHAIN_PF128
-#define PMX_CHAIN_PF128 0    // how far ahead the gA waves of <RS, CHAIN> request the pieces of a chain's previous sum (see the loop); the A/B builds set it
-#endif
 constexpr int W8_NCB = 4;
 constexpr int W8_S_HALF = 2 * V5_S_TERM;            // [h][l] images of one k half of a 32-column block
 constexpr int W8_SL_BYTES = 2 * W8_S_HALF;          // both halves: 16 KB per block
@@ -230,7 +227,7 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_k128(GradK128Args a)
     using yes = std::integral_constant<bool, true>;
     using no = std::integral_constant<bool, false>;
     if (producer) {
-        k1_set_priority(-a.consPrio);      // (PMX_K1_PRIO < 0: the producers instead -- A/B only)
+        k1_set_priority(-a.consPrio);      // (a negative level: the producers instead -- no launch asks for it)
         // ================================ producers: P = A S and R ================================================
         f32x16 p0, p1;
         float yE[16], yO[16];
@@ -532,37 +529,9 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_k128(GradK128Args a)
                 if constexpr (CHAIN) link.look();
                 consumeA(s - 2, c1{});
                 if constexpr (CHAIN) link.wait();
-                // [r6] PMX_CHAIN_PF128: how far ahead of its add a piece of the previous sum is requested (the adds stand where they stood: same sums, same order).
-                //   0: in front of the half block of MFMAs it is added behind (rounds 4-5: 24 MFMAs = ~0.4 us per round trip)
-                //   1: one buffer, every piece requested as soon as the buffer is free -- the first behind the arrival check, the third behind the second's add
-                //   2: two buffers (+ 32 registers): two pieces in flight, a whole slot per round trip
-                if constexpr (CHAIN && PMX_CHAIN_PF128 == 2) {
-                    float pa[32], pb[32];
-                    if (link.cadd) { chain_fetch(prow, 0, 0, pa); chain_fetch(prow, 0, 1, pb); }
-                    sync(); ++s;
-                    consumeA_ks(s - 2, c2{}, c0{});
-                    if (link.cadd) { chain_add(0, 0, pa); chain_fetch(prow, 1, 0, pa); }
-                    consumeA_ks(s - 2, c2{}, c1{});
-                    if (link.cadd) { chain_add(0, 1, pb); chain_fetch(prow, 1, 1, pb); }
-                    sync(); ++s;
-                    consumeA_ks(s - 2, c3{}, c0{});
-                    if (link.cadd) chain_add(1, 0, pa);
-                    consumeA_ks(s - 2, c3{}, c1{});
-                    if (link.cadd) chain_add(1, 1, pb);
-                } else if constexpr (CHAIN && PMX_CHAIN_PF128 == 1) {
-                    float pv[32];
-                    if (link.cadd) chain_fetch(prow, 0, 0, pv);
-                    sync(); ++s;
-                    consumeA_ks(s - 2, c2{}, c0{});
-                    if (link.cadd) { chain_add(0, 0, pv); chain_fetch(prow, 0, 1, pv); }
-                    consumeA_ks(s - 2, c2{}, c1{});
-                    if (link.cadd) { chain_add(0, 1, pv); chain_fetch(prow, 1, 0, pv); }
-                    sync(); ++s;
-                    consumeA_ks(s - 2, c3{}, c0{});
-                    if (link.cadd) { chain_add(1, 0, pv); chain_fetch(prow, 1, 1, pv); }
-                    consumeA_ks(s - 2, c3{}, c1{});
-                    if (link.cadd) chain_add(1, 1, pv);
-                } else if constexpr (CHAIN) {
+                // [r6] each piece of the previous sum is requested in front of the half block of MFMAs it is added behind (rounds 4-5: 24 MFMAs = ~0.4 us per
+                // round trip); requesting them one or two buffers ahead measured nothing or spilled (profiles/r06_q_chain_prefetch_ab.txt)
+                if constexpr (CHAIN) {
                     sync(); ++s;
                     float pv[32];
                     if (link.cadd) chain_fetch(prow, 0, 0, pv);
@@ -860,10 +829,9 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_k128(GradK128Args a)
 }
 
 // host side -----------------------------------------------------------------------------------------
-// shapes the kernel takes (PMX_K1_K128=0: off, the exact-fp32 kernel instead -- tuning A/B)
+// shapes the kernel takes
 bool grad_k128_applies(int64_t M, int64_t N, int64_t K) {
-    if (K != 128 || M % V5_BM != 0 || N % (W8_NCB * V5_BN) != 0) return false;
-    return !(getenv("PMX_K1_K128") && atoi(getenv("PMX_K1_K128")) == 0);
+    return K == 128 && M % V5_BM == 0 && N % (W8_NCB * V5_BN) == 0;
 }
 GradPlan grad_plan_k128(int64_t M, int64_t N) {
     GradPlan p{};
@@ -871,20 +839,11 @@ GradPlan grad_plan_k128(int64_t M, int64_t N) {
     p.BN = V5_BN;
     const int64_t panels = M / V5_BM;
     p.gridY = (int)(N / (W8_NCB * V5_BN));
-    const int wantWG = getenv("PMX_K1_WGS") ? atoi(getenv("PMX_K1_WGS")) : 256;   // one resident workgroup per CU
-    plan_row_regions(panels, p.gridY, wantWG, &p.RP, &p.gridX);
+    plan_row_regions(panels, p.gridY, 256, &p.RP, &p.gridX);    // one resident workgroup per CU
     p.nSlabA = p.gridY;
     p.nSlabS = p.gridX;
     p.ldsBytes = W8_LDS_BYTES;
     return p;
-}
-// panels between the rotations of neighbouring chain members (PMX_K128_STRIDE: A/B)
-int grad_k128_chain_stride(const GradPlan& p, int chainL) {
-    if (chainL <= 0) return 1;
-    const int want = getenv("PMX_K128_STRIDE") ? atoi(getenv("PMX_K128_STRIDE")) : 1;   // measured (profiles/r04_a_k128_chain_ab.txt): 1 beats 2 -- the predecessor's sum is still in L2
-    int sg = p.RP / chainL;
-    if (sg > want) sg = want;
-    return sg < 1 ? 1 : sg;
 }
 template <bool HASW, bool CHAIN, bool HH = false, bool RS = false>
 static hipError_t grad_launch_k128_t(const GradK128Args& a, hipStream_t stream) {
@@ -893,11 +852,13 @@ static hipError_t grad_launch_k128_t(const GradK128Args& a, hipStream_t stream) 
     hipLaunchKernelGGL((k_grad_f16_k128<HASW, CHAIN, HH, RS>), dim3(a.gridX * a.gridY), dim3(V5_THREADS), W8_LDS_BYTES, stream, a);
     return hipGetLastError();
 }
-hipError_t grad_launch_k128(const GradK128Args& a, hipStream_t stream) {
-    if (a.hh && a.W == nullptr && (a.doA & 1) && a.doS && !(getenv("PMX_K1_ROLE_SPLIT") && atoi(getenv("PMX_K1_ROLE_SPLIT")) == 0))    // <RS>: both gradients wanted (PMX_K1_ROLE_SPLIT=0: A/B)
-        return a.chainL > 0 ? grad_launch_k128_t<false, true, true, true>(a, stream) : grad_launch_k128_t<false, false, true, true>(a, stream);
-    if (a.hh && a.W == nullptr && ((a.doA & 1) || a.doS))      // (the loss-only pass has nowhere to put a correction: two terms)
+// inst (k1_instance): K1_HH or K1_PLAIN
+hipError_t grad_launch_k128(const GradK128Args& a, K1Inst inst, hipStream_t stream) {
+    if (inst == K1_HH) {
+        if ((a.doA & 1) && a.doS && !(getenv("PMX_K1_ROLE_SPLIT") && atoi(getenv("PMX_K1_ROLE_SPLIT")) == 0))    // <RS>: both gradients wanted (PMX_K1_ROLE_SPLIT=0: A/B)
+            return a.chainL > 0 ? grad_launch_k128_t<false, true, true, true>(a, stream) : grad_launch_k128_t<false, false, true, true>(a, stream);
         return a.chainL > 0 && (a.doA & 1) ? grad_launch_k128_t<false, true, true>(a, stream) : grad_launch_k128_t<false, false, true>(a, stream);
+    }
     if (a.chainL > 0 && (a.doA & 1))
         return a.W != nullptr ? grad_launch_k128_t<true, true>(a, stream) : grad_launch_k128_t<false, true>(a, stream);
     return a.W != nullptr ? grad_launch_k128_t<true, false>(a, stream) : grad_launch_k128_t<false, false>(a, stream);

@@ -125,14 +125,8 @@ struct pmx_ctx {
     float* Tg[2][PMX_MAX_G] = {};           // bsdmm with a user-defined proxs_g member: its argument X + U_i, then its result (host round trip)
     float* Tf[2] = {};                      // bsdmm with a user-defined prox_f: its argument, then its result
     unsigned long long* k1prof = nullptr;  // tuning: phase cycle sums (PMX_K1_PROF=1)
-    bool use_small = false;                // small problem (K <= 16, few million entries): k_grad_small in every mode
-    bool use_bf16 = false;                 // split-bf16 kernel (mode BF16X3 / F16X2 and K <= 64), else exact fp32 MFMA
-    bool use_f16 = false;                  // mode F16X2 at a shape the two-term fp16 kernel takes
-    bool k128 = false;                     // mode F16X2, K = 128 at a shape k_grad_f16_k128 takes
-    bool k32f16 = false;                   // mode F16X2, K = 32, M % 128 = 0, N % 256 = 0: k_grad_f16_k32 (no weights)
-    bool f32pc = false;                    // exact-fp32 arithmetic at a shape the producer / consumer kernel k_grad_f32_pc takes
-    bool f16_fell_back = false;            // use_f16, but the last launch ran the split-bf16 kernel (Y / W not fetchable in 8-byte pairs)
-    bool f16_scales = false;               // use_f16 || k128: the K1 kernel needs the factor maxima (absmax) and max|Y|
+    K1Kind k1 = K1_F32;                    // which K1 family runs (select_k1); the predicates below say what it needs
+    bool k1_pairs = true;                  // Y (and W) could be fetched in 8-byte pairs at the last K1 launch (K1_F16_V8: else its v7 fall-back ran)
     // [r4] the two-term fp16 kernels refuse a launch whose residual bound K max|A| max|S| exceeds rangeRatio max|Y| (f16_range_fault,
     // k_grad_f16_v8.hip): the context then continues in exact fp32 on the same frame (k1_leave_f16).  PMX_F16_RANGE=n: ratio 2^n, 0: no check
     float rangeRatio = 65536.f;
@@ -161,7 +155,8 @@ struct pmx_ctx {
     bool gram_fresh[2] = {false, false};   // bsdmm: gramPart[f] holds the partial Gram matrices of the CURRENT factor f (left by k_bsdmm_update)
     bool gram_in_update = true;            // PMX_GRAM_IN_UPDATE=0 (read at context creation): off
     bool fold_in_k1 = true;                // [r6] pgm: the step rule's Gram fold rides in K1's first workgroups where it can (PMX_FOLD_IN_K1=0: off, A/B)
-    K1GramFold k1_fold{};                  //   what the NEXT K1 launch carries (part == nullptr: nothing); set by pgm_enqueue_iteration, consumed by enqueue_grad_once
+    K1GramFold k1_fold{};                  //   what the NEXT K1 launch carries (part == nullptr: nothing); set by pgm_enqueue_iteration for a kind that carries
+                                           //   it (k1_carries_fold), consumed by enqueue_grad_once whatever happens
     bool decide_pending = false;           // pgm: the stopping test of the last enqueued iteration has not been enqueued yet (it rides in the
                                            // next k_gram_reduce launch, or pgm_flush_decide() launches it at the end of a chunk)
     __bf16* Bp[2] = {nullptr, nullptr};    // presplit terms, row-major   [3][rowsPad][KP]
@@ -176,7 +171,6 @@ struct pmx_ctx {
     int chainFaults = 0;                   // times the chained mode was left after a fault
     // test hooks, read from the environment ONCE when the context is created (never on a launch path):
     int hook_inject_k1 = 0;                //   PMX_INJECT_K1_FAULT=n: the n-th chained K1 launch reports a fault
-    int k1_prio = -999;                    // [r6] s_setprio level of K1's consumer waves (k1_set_priority); -999: the kernel's own default (k1_prio_for), PMX_K1_PRIO overrides
     std::string hook_tail_lockfile;        //   PMX_TAIL_LOCKFILE: several processes on ONE GPU take turns with the persistent tail
     bool tail_fused = false;               // adaprox: the iteration tail runs as one persistent kernel (k_ada_tail)
     GridBar* gridbar = nullptr;            // its barrier state
@@ -367,27 +361,36 @@ static void choose_frame(int mode, int64_t M, int64_t N, int64_t K, int64_t* Mk,
     *Mk = m; *Nk = n;
 }
 
+// what a K1 family needs and does
+static bool k1_fp16(K1Kind k) { return k == K1_F16_V8 || k == K1_F16_K128 || k == K1_F16_K32; }      // factor maxima (absmax), max |Y|, max |W|, the range guard
+static bool k1_chains(K1Kind k) { return k == K1_F32PC || k == K1_BF16_V7 || k == K1_F16_V8 || k == K1_F16_K128; }   // gA may be summed along chains
+static bool k1_tuned(K1Kind k) { return k1_chains(k) || k == K1_F16_K32; }                          // a producer / consumer kernel
+static bool k1_carries_fold(K1Kind k) { return k == K1_F16_K32 || k == K1_F32PC; }                  // the step rule's Gram fold rides in it
+static bool k1_small(K1Kind k) { return k == K1_SMALL || k == K1_F64_SMALL; }
+
 // which K1 runs on the frame Mk x Nk, its grid, and whether gA is summed along chains there
 static void select_k1(pmx_ctx* c, int64_t Mk, int64_t Nk, int ncu) {
     const int64_t M = c->M, N = c->N, K = c->Kk;
     const int mode = c->mode;
-    c->use_small = grad_small_applies(M, N, c->K);
-    c->use_bf16 = (mode == PMX_MODE_BF16X3 || mode == PMX_MODE_F16X2) && K <= 64 && !c->use_small;
-    c->plan = c->use_small ? grad_plan_small(M, N, K) : (c->use_bf16 ? grad_plan_bf16(Mk, Nk, K) : grad_plan_f32(Mk, Nk, K));
-    c->use_f16 = mode == PMX_MODE_F16X2 && c->use_bf16 && grad_bf16_takes_weights(c->plan, Mk, Nk, K);   // same shapes as v7
-    c->k128 = mode == PMX_MODE_F16X2 && !c->use_small && grad_k128_applies(Mk, Nk, K);
-    if (c->k128) c->plan = grad_plan_k128(Mk, Nk);
-    c->k32f16 = mode == PMX_MODE_F16X2 && !c->use_small && grad_f16_k32_applies(Mk, Nk, K);
-    if (c->k32f16) { c->plan = grad_plan_f16_k32(Mk, Nk); c->use_bf16 = false; c->use_f16 = false; }
-    c->f32pc = !c->use_small && !c->use_bf16 && !c->k128 && !c->k32f16 && grad_f32pc_applies(Mk, Nk, K);
-    if (c->f32pc) c->plan = grad_plan_f32pc(Mk, Nk, K);
-    c->f16_scales = c->use_f16 || c->k128 || c->k32f16;
+    if (grad_small_applies(M, N, c->K)) {
+        c->k1 = K1_SMALL; c->plan = grad_plan_small(M, N, K);
+    } else if (mode == PMX_MODE_F16X2 && grad_f16_k32_applies(Mk, Nk, K)) {
+        c->k1 = K1_F16_K32; c->plan = grad_plan_f16_k32(Mk, Nk);
+    } else if (mode == PMX_MODE_F16X2 && grad_k128_applies(Mk, Nk, K)) {
+        c->k1 = K1_F16_K128; c->plan = grad_plan_k128(Mk, Nk);
+    } else if ((mode == PMX_MODE_BF16X3 || mode == PMX_MODE_F16X2) && K <= 64) {
+        c->plan = grad_plan_bf16(Mk, Nk, K);
+        c->k1 = !grad_bf16_reads_fp32(c->plan, Mk, Nk, K) ? K1_BF16 : mode == PMX_MODE_F16X2 ? K1_F16_V8 : K1_BF16_V7;
+    } else if (grad_f32pc_applies(Mk, Nk, K)) {
+        c->k1 = K1_F32PC; c->plan = grad_plan_f32pc(Mk, Nk, K);
+    } else {
+        c->k1 = K1_F32; c->plan = grad_plan_f32(Mk, Nk, K);
+    }
     c->nSlabA = c->plan.nSlabA;
     c->nSlabS = c->plan.nSlabS;
     c->chainL = 0;
-    const bool v7_shape = c->use_bf16 && grad_bf16_takes_weights(c->plan, Mk, Nk, K);     // k_grad_bf16_v7 / k_grad_f16_v8: the chained frame
-    if (v7_shape || c->f32pc || c->k128) {
-        c->chainL = grad_chain_length(c->plan, Mk, ncu, (c->use_f16 || c->k128) ? 16 : 32);
+    if (k1_chains(c->k1)) {
+        c->chainL = grad_chain_length(c->plan, Mk, ncu, (c->k1 == K1_F16_V8 || c->k1 == K1_F16_K128) ? 16 : 32);
         if (c->chainL > 0) c->nSlabA = c->plan.gridY / c->chainL;
     }
 }
@@ -427,7 +430,6 @@ extern "C" int pmx_ctx_create(pmx_ctx** out, int device, int64_t M, int64_t N, i
     if (const char* e = getenv("PMX_GRAM_IN_UPDATE")) c->gram_in_update = atoi(e) != 0;
     if (const char* e = getenv("PMX_INJECT_K1_FAULT")) c->hook_inject_k1 = atoi(e);
     if (const char* e = getenv("PMX_FOLD_IN_K1")) c->fold_in_k1 = atoi(e) != 0;
-    if (const char* e = getenv("PMX_K1_PRIO")) c->k1_prio = atoi(e);
     if (const char* e = getenv("PMX_TAIL_LOCKFILE")) c->hook_tail_lockfile = e;
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ncu = 0;
@@ -445,11 +447,10 @@ extern "C" int pmx_ctx_create(pmx_ctx** out, int device, int64_t M, int64_t N, i
         choose_frame(mode, M, N, c->Kk, &c->Mk, &c->Nk);
         c->framed = c->Mk != M || c->Nk != N;
         select_k1(c, c->Mk, c->Nk, ncu);
-        const bool tuned = c->k128 || c->k32f16 || c->f32pc || (c->use_bf16 && grad_bf16_takes_weights(c->plan, c->Mk, c->Nk, c->Kk));
-        if (c->Kk == K || tuned) break;
+        if (c->Kk == K || k1_tuned(c->k1)) break;
         c->Kk = K;                                                   // (padding K buys nothing where the shape keeps the guarded kernels)
     }
-    if (c->framed && c->chainL == 0 && (c->use_bf16 || c->f32pc || c->k128)) {
+    if (c->framed && c->chainL == 0 && k1_chains(c->k1)) {
         // a frame the chained accumulation of gA does not take (e.g. 125 panels x 63 column regions): a few more panels / column
         // regions often make one that it does (128 x 64) -- worth up to 6 % more entries (the chain is ~10 % of an iteration: one
         // gA slab per 16 column regions instead of one each, for K1 to write and the update kernel to fold)
@@ -471,8 +472,7 @@ extern "C" int pmx_ctx_create(pmx_ctx** out, int device, int64_t M, int64_t N, i
     if (mode == PMX_MODE_F64) {              // fp64 context: its own arrays and kernels (k_small_f64.hip), nothing of the fp32 state
         c->f64 = true;
         c->f64big = !f64_small;
-        c->use_small = f64_small;
-        c->use_bf16 = c->use_f16 = c->k128 = c->f32pc = c->f16_scales = false;
+        c->k1 = f64_small ? K1_F64_SMALL : K1_F64_BIG;
         c->chainL = 0;
         if (c->f64big) {                     // k_big_f64.hip: one MFMA pass per gradient, a few slabs each
             pass64_plan(M, N, (int)K, &c->nsplit64[0], &c->bps64[0]);
@@ -515,16 +515,16 @@ extern "C" int pmx_ctx_create(pmx_ctx** out, int device, int64_t M, int64_t N, i
     }
     int rc = PMX_OK;
     if (c->chainL > 0) rc = dallocT(c, &c->chainFlags, (size_t)(c->plan.gridX * c->plan.gridY / c->chainL) * c->plan.RP * 4);
-    if (c->f16_scales) rc = dallocT(c, &c->absmax, (size_t)3 * 256);
-    if (rc == PMX_OK && c->f16_r3 == 2 && (c->use_f16 || c->k128)) {          // <HH> instances: the correction's matrices and slabs
+    if (k1_fp16(c->k1)) rc = dallocT(c, &c->absmax, (size_t)3 * 256);
+    if (rc == PMX_OK && k1_instance(c->k1, c->f16_r3, false, true, true) == K1_HH) {          // <HH> instances can run: the correction's matrices and slabs
         rc = dallocT(c, &c->fixPart, (size_t)2 * GFIX_PARTS * 2 * c->Kk * c->Kk, false);
         if (rc == PMX_OK) rc = dallocT(c, &c->fixQ, (size_t)4 * c->Kk * c->Kk);
         for (int j = 0; j < 2 && rc == PMX_OK; ++j) rc = dallocT(c, &c->fixSlab[j], (size_t)c->rowsK[j] * c->Kk);
         if (rc == PMX_OK && getenv("PMX_GFIX_PROF")) rc = dallocT(c, &c->fixProf, 16);
     }
-    for (int t = 0; t < 2 && rc == PMX_OK && c->k128; ++t) rc = dallocT(c, &c->A16[t], (size_t)Mk * c->Kk, c->framed || c->Kk != K);   // (framed: the rows behind M / the columns behind K stay zero)
+    for (int t = 0; t < 2 && rc == PMX_OK && c->k1 == K1_F16_K128; ++t) rc = dallocT(c, &c->A16[t], (size_t)Mk * c->Kk, c->framed || c->Kk != K);   // (framed: the rows behind M / the columns behind K stay zero)
     for (int j = 0; j < 2 && rc == PMX_OK && c->Kk != K; ++j) rc = dallocT(c, &c->Xk[j], (size_t)c->rowsK[j] * c->Kk);          // K1's zero-padded operands
-    if (c->use_bf16) {
+    if (c->k1 == K1_BF16 || c->k1 == K1_BF16_V7 || c->k1 == K1_F16_V8) {
         for (int j = 0; j < 2 && rc == PMX_OK; ++j) {
             c->rowsPad[j] = (c->rowsK[j] + 127) / 128 * 128;
             rc = dallocT(c, &c->Bp[j], (size_t)3 * c->rowsPad[j] * c->KP, false);
@@ -656,7 +656,19 @@ extern "C" int pmx_get_phase_timing(pmx_ctx* c, double ms[6], int* iterations) {
 
 extern "C" int pmx_k1_info(pmx_ctx* c, int info[8]) {
     if (!c || !info) FAIL(PMX_E_INVALID, "NULL argument");
-    info[0] = c->f64big ? 13 : c->f64 ? 7 : c->k32f16 ? (c->f16_r3 ? 10 : 8) : c->use_small ? 4 : (c->k128 ? (c->f16_r3 == 2 && !c->W && c->fixPart ? 12 : 5) : (c->use_f16 && !c->f16_fell_back ? (c->f16_r3 && !c->W ? (c->f16_r3 == 2 && c->fixPart ? 11 : 9) : 2) : (c->use_bf16 ? 1 : (c->f32pc ? 6 : 0))));
+    // the instance a gradient pass runs now (K1_F16_V8: with the pair fetches of the last launch)
+    const K1Inst inst = k1_instance(c->k1, c->f16_r3, c->W != nullptr, true, c->k1_pairs);
+    switch (c->k1) {
+    case K1_F32: info[0] = 0; break;
+    case K1_BF16: case K1_BF16_V7: info[0] = 1; break;
+    case K1_F16_V8: info[0] = inst == K1_V7 ? 1 : inst == K1_HH ? 11 : inst == K1_R3 ? 9 : 2; break;      // (3: retired)
+    case K1_SMALL: info[0] = 4; break;
+    case K1_F16_K128: info[0] = inst == K1_HH ? 12 : 5; break;
+    case K1_F32PC: info[0] = 6; break;
+    case K1_F64_SMALL: info[0] = 7; break;
+    case K1_F16_K32: info[0] = inst == K1_R3 ? 10 : 8; break;
+    case K1_F64_BIG: info[0] = 13; break;
+    }
     info[1] = c->chainL;
     info[2] = c->nSlabA;
     info[3] = c->nSlabS;
@@ -683,7 +695,7 @@ extern "C" int pmx_ctx_sync(pmx_ctx* c) {
 
 // max |Y| for the fp16 path's residual scale (one pass over Y, once)
 static int measure_ymax(pmx_ctx* c) {
-    if (!c->f16_scales) return PMX_OK;
+    if (!k1_fp16(c->k1)) return PMX_OK;
     launch_absmax_pitched(c->Y, c->ldY, c->M, c->N, c->absmax + 512, c->stream);
     HIP_CHECK(hipGetLastError());
     float h[256];
@@ -742,7 +754,7 @@ extern "C" int pmx_set_Y_device(pmx_ctx* c, const float* dY, int64_t ld, int cop
 // max(1, max |W|) for the fp16 path's residual scale
 static int measure_wmax(pmx_ctx* c) {
     c->wmax = 1.f;
-    if (!c->f16_scales || !c->W) return PMX_OK;      // (the two-term fp16 kernels, K = 64 and K = 128: max |W| enters R's scale)
+    if (!k1_fp16(c->k1) || !c->W) return PMX_OK;      // (the two-term fp16 kernels, K = 64 and K = 128: max |W| enters R's scale)
     launch_absmax_pitched(c->W, c->ldW, c->M, c->N, c->absmax + 512, c->stream);
     HIP_CHECK(hipGetLastError());
     float h[256];
@@ -760,8 +772,8 @@ static int set_W_common(pmx_ctx* c, const float* W, int64_t ld, int from_host, i
     if (!c) FAIL(PMX_E_INVALID, "ctx is NULL");
     if (!W) { c->W = nullptr; c->ldW = 0; c->wmax = 1.f; return PMX_OK; }
     if (ld < c->N) FAIL(PMX_E_INVALID, "ld %lld < N", (long long)ld);
-    if (c->k32f16) FAIL(PMX_E_UNSUPPORTED, "k_grad_f16_k32 takes no weights; create the context with PMX_MODE_F32");
-    if (c->use_bf16 && !grad_bf16_takes_weights(c->plan, c->Mk, c->Nk, c->Kk))
+    if (c->k1 == K1_F16_K32) FAIL(PMX_E_UNSUPPORTED, "k_grad_f16_k32 takes no weights; create the context with PMX_MODE_F32");
+    if (c->k1 == K1_BF16)
         FAIL(PMX_E_UNSUPPORTED, "a weighted likelihood in a split-precision mode needs K = 64 with M %% 128 = 0, N %% 256 = 0 or K = 128 with M %% 128 = 0, N %% 128 = 0; create the context with PMX_MODE_F32");
     if (c->comm) FAIL(PMX_E_UNSUPPORTED, "weights are not supported in row-sharded runs");
     HIP_CHECK(hipSetDevice(c->device));
@@ -1104,27 +1116,10 @@ static EigArgs small_eig_args(pmx_ctx* c, const float* A, const float* St, bool 
     e.rows[0] = c->M; e.rows[1] = c->N;
     return e;
 }
-// small problems: K1 and both step rules of a pgm iteration in ONE launch (k_small_front)
-static int enqueue_small_front(pmx_ctx* c, const float* A, const float* St, double scale) {
-    const bool timed = c->timing && (c->timing_seq++ % (unsigned)c->timing_stride) == 0 && c->ev_used + 2 <= c->ev.size();
-    const GradArgs g = small_grad_args(c, A, St, 1, 1);
-    const EigArgs e = small_eig_args(c, A, St, true, true, scale);
-    if (timed) HIP_CHECK(hipEventRecord(c->ev[c->ev_used], c->stream));
-    HIP_CHECK(launch_small_front(c->plan, g, e, c->stream));
-    c->nloss = c->plan.gridX * c->plan.gridY;
-    if (timed) {
-        HIP_CHECK(hipEventRecord(c->ev[c->ev_used + 1], c->stream));
-        c->ev_used += 2;
-    }
-    return PMX_OK;
-}
 
 // [r6] Consumer-wave priority per tuned K1 (same-box A/B, profiles/r06_b_setprio_ab.txt): K = 128 and K = 32 gain 1-2.5 % at level 1 (the consumers
 // are the pole of the slot and the younger half of the workgroup), K = 64 shows nothing outside the noise and keeps 0.
-static int k1_prio_for(const pmx_ctx* c, int kk) {
-    if (c->k1_prio != -999) return c->k1_prio;
-    return kk == 64 ? 0 : 1;
-}
+static int k1_prio_for(int kk) { return kk == 64 ? 0 : 1; }
 
 // absmax_fresh: the factor maxima in c->absmax were written by the kernel that produced A and St (k_ada_finish)
 static int enqueue_gfix(pmx_ctx* c, const float* A, const float* St, int doA, int doS, hipStream_t stream) {
@@ -1143,7 +1138,69 @@ static int enqueue_gfix(pmx_ctx* c, const float* A, const float* St, int doA, in
     return PMX_OK;
 }
 
+// the factor maxima of A and St in c->absmax: the operand scales of the two-term fp16 kernels
+static void enqueue_absmax(pmx_ctx* c, const float* A, const float* St) {
+    AbsmaxArgs am{};
+    am.X[0] = A; am.X[1] = St;
+    am.count[0] = c->M * c->Kk; am.count[1] = c->N * c->Kk;
+    am.out = c->absmax;
+    am.status = c->dstatus;
+    launch_absmax(am, c->stream);
+}
+// the arrival words of the next chained launch (monotonic: launch n counts from 64 n; zeroed before they run out of bits)
+template <class Args>
+static int chain_arm(pmx_ctx* c, Args& g) {
+    if (c->chainSeq >= (1u << 21)) {
+        HIP_CHECK(hipMemsetAsync(c->chainFlags, 0, (size_t)(c->plan.gridX * c->plan.gridY / c->chainL) * c->plan.RP * 4 * sizeof(unsigned), c->stream));
+        c->chainSeq = 0;
+    }
+    g.chainL = c->chainL; g.chainFlags = c->chainFlags; g.chainBase = (++c->chainSeq) * 64u; g.wstatus = c->dstatus;
+    g.chainInject = c->hook_inject_k1 > 0 && (int)c->chainSeq == c->hook_inject_k1;   // tests (read once, at pmx_ctx_create)
+    return PMX_OK;
+}
+// the K1 launch, between two timing events on every timing_stride-th call (pmx_set_timing: they bracket K1 alone)
+template <class Launch>
+static int k1_timed(pmx_ctx* c, Launch&& launch) {
+    const bool timed = c->timing && (c->timing_seq++ % (unsigned)c->timing_stride) == 0 && c->ev_used + 2 <= c->ev.size();
+    if (timed) HIP_CHECK(hipEventRecord(c->ev[c->ev_used], c->stream));
+    HIP_CHECK(launch());
+    c->nloss = c->plan.gridX * c->plan.gridY;
+    if (timed) {
+        HIP_CHECK(hipEventRecord(c->ev[c->ev_used + 1], c->stream));
+        c->ev_used += 2;
+    }
+    return PMX_OK;
+}
+static GradV4Args v4_args(pmx_ctx* c, const float* A, const float* St, int doA, int doS) {
+    GradV4Args g{};
+    g.Y = c->Y; g.ldY = c->ldY;
+    g.A = A; g.St = St;
+    g.slabA = c->slab[0]; g.slabS = c->slab[1];
+    g.lossPart = c->lossPart;
+    g.status = c->dstatus;
+    g.M = (int)c->Mk; g.N = (int)c->Nk;
+    g.RP = c->plan.RP;
+    g.doA = doA; g.doS = doS;
+    g.gridX = c->plan.gridX; g.gridY = c->plan.gridY;
+    return g;
+}
+// the two-term fp16 kernels' scales and range guard (K = 32 / 64)
+static void v4_f16_args(pmx_ctx* c, GradV4Args& g, int kk) {
+    g.absmax = c->absmax; g.ymax = c->ymax; g.wmax = c->wmax;      // (K1_F16_K32 takes no weights: wmax is 1)
+    g.wstatus = c->dstatus; g.rangeRatio = c->rangeRatio; g.r3 = c->f16_r3; g.consPrio = k1_prio_for(kk);
+}
+
+// small problems: K1 and both step rules of a pgm iteration in ONE launch (k_small_front)
+static int enqueue_small_front(pmx_ctx* c, const float* A, const float* St, double scale) {
+    const GradArgs g = small_grad_args(c, A, St, 1, 1);
+    const EigArgs e = small_eig_args(c, A, St, true, true, scale);
+    return k1_timed(c, [&] { return launch_small_front(c->plan, g, e, c->stream); });
+}
+
 static int enqueue_grad_once(pmx_ctx* c, const float* A, const float* St, int doA, int doS, bool absmax_fresh) {
+    // the step rule's Gram fold (pgm_enqueue_iteration) is this launch's, carried or not: left armed it would ride in a later launch
+    const K1GramFold fold = c->k1_fold;
+    c->k1_fold = K1GramFold{};
     if (c->host_grad) return PMX_OK;       // a user `grad` callable: its result is already in G (see slab_ref)
     if (c->Kk != c->K) {                   // K1 runs the next tuned K: its operands are zero-padded copies of the factors
         PadArgs pa{};
@@ -1155,18 +1212,14 @@ static int enqueue_grad_once(pmx_ctx* c, const float* A, const float* St, int do
         launch_pad_factors(pa, c->stream);
         A = c->Xk[0]; St = c->Xk[1];
     }
-    const int64_t Kq = c->Kk;              // K as K1 sees it (rows of A / St are Kq floats apart)
-    bool fix_pending = false;              // an <HH> kernel was launched: its correction slab is owed (behind the timing events: they bracket K1 alone)
-    const bool timed = c->timing && (c->timing_seq++ % (unsigned)c->timing_stride) == 0 && c->ev_used + 2 <= c->ev.size();
-    if (c->k128) {
-        AbsmaxArgs am{};
-        am.X[0] = A; am.X[1] = St;
-        am.count[0] = c->M * Kq; am.count[1] = c->N * Kq;
-        am.out = c->absmax;
-        am.status = c->dstatus;
-        if (!absmax_fresh) launch_absmax(am, c->stream);
+    const bool grad = (doA & 1) || doS;
+    if (k1_fp16(c->k1) && !absmax_fresh) enqueue_absmax(c, A, St);      // (fresh: k_ada_finish left the maxima of these factors)
+    K1Inst inst = K1_PLAIN;
+    int rc = PMX_OK;
+    switch (c->k1) {
+    case K1_F16_K128: {
         SplitAArgs sp{};
-        sp.X = A; sp.count = c->M * Kq; /* (a frame's extra rows stay zero) */ sp.absmax = c->absmax; sp.H = c->A16[0]; sp.L = c->A16[1]; sp.status = c->dstatus;
+        sp.X = A; sp.count = c->M * c->Kk; /* (a frame's extra rows stay zero) */ sp.absmax = c->absmax; sp.H = c->A16[0]; sp.L = c->A16[1]; sp.status = c->dstatus;
         launch_split_a_f16(sp, c->stream);
         GradK128Args g{};
         g.Y = c->Y; g.ldY = c->ldY;
@@ -1182,52 +1235,47 @@ static int enqueue_grad_once(pmx_ctx* c, const float* A, const float* St, int do
         g.W = c->W; g.ldW = c->ldW; g.wmax = c->wmax;
         g.wstatus = c->dstatus; g.rangeRatio = c->rangeRatio;
         if (c->chainL > 0 && (doA & 1)) {    // k_grad_f16_k128<.., CHAIN>
-            if (c->chainSeq >= (1u << 21)) {   // arrival words would run out of bits: start over
-                HIP_CHECK(hipMemsetAsync(c->chainFlags, 0, (size_t)(c->plan.gridX * c->plan.gridY / c->chainL) * c->plan.RP * 4 * sizeof(unsigned), c->stream));
-                c->chainSeq = 0;
-            }
-            g.chainL = c->chainL; g.chainStride = grad_k128_chain_stride(c->plan, c->chainL);
-            g.chainFlags = c->chainFlags; g.chainBase = (++c->chainSeq) * 64u; g.wstatus = c->dstatus;
-            g.chainInject = c->hook_inject_k1 > 0 && (int)c->chainSeq == c->hook_inject_k1;   // tests (read once, at pmx_ctx_create)
+            g.chainStride = 1;               // panels between neighbouring members' rotations (1 beats 2: profiles/r04_a_k128_chain_ab.txt)
+            rc = chain_arm(c, g);
         }
-        g.hh = c->f16_r3 == 2 && c->W == nullptr && c->fixPart != nullptr && ((doA & 1) || doS);     // (the launcher's own test: gradient passes only)
-        g.consPrio = k1_prio_for(c, 128);
-        fix_pending = g.hh != 0;
-        if (timed) HIP_CHECK(hipEventRecord(c->ev[c->ev_used], c->stream));
-        HIP_CHECK(grad_launch_k128(g, c->stream));
-        c->nloss = c->plan.gridX * c->plan.gridY;
-    } else if (c->k32f16) {
-        AbsmaxArgs am{};
-        am.X[0] = A; am.X[1] = St;
-        am.count[0] = c->M * Kq; am.count[1] = c->N * Kq;
-        am.out = c->absmax;
-        am.status = c->dstatus;
-        if (!absmax_fresh) launch_absmax(am, c->stream);
-        GradV4Args g{};
-        g.Y = c->Y; g.ldY = c->ldY;
-        g.A = A; g.St = St;
-        g.slabA = c->slab[0]; g.slabS = c->slab[1];
-        g.lossPart = c->lossPart;
-        g.status = c->dstatus;
-        g.M = (int)c->Mk; g.N = (int)c->Nk;
-        g.RP = c->plan.RP;
-        g.doA = doA; g.doS = doS;
-        g.gridX = c->plan.gridX; g.gridY = c->plan.gridY;
-        g.absmax = c->absmax; g.ymax = c->ymax; g.wmax = 1.f;
-        g.wstatus = c->dstatus; g.rangeRatio = c->rangeRatio;
-        g.r3 = c->f16_r3;
-        g.consPrio = k1_prio_for(c, 32);
-        g.fold = c->k1_fold; c->k1_fold = K1GramFold{};
-        if (timed) HIP_CHECK(hipEventRecord(c->ev[c->ev_used], c->stream));
-        HIP_CHECK(grad_launch_f16_k32(g, c->stream));
-        c->nloss = c->plan.gridX * c->plan.gridY;
-    } else if (c->use_bf16) {
+        inst = k1_instance(c->k1, c->f16_r3, c->W != nullptr, grad, true);
+        g.hh = inst == K1_HH;
+        g.consPrio = k1_prio_for(128);
+        if (rc == PMX_OK) rc = k1_timed(c, [&] { return grad_launch_k128(g, inst, c->stream); });
+        break;
+    }
+    case K1_F16_K32: {
+        GradV4Args g = v4_args(c, A, St, doA, doS);
+        v4_f16_args(c, g, 32);
+        g.fold = fold;
+        inst = k1_instance(c->k1, c->f16_r3, false, grad, true);
+        rc = k1_timed(c, [&] { return grad_launch_f16_k32(g, inst, c->stream); });
+        break;
+    }
+    case K1_F16_V8:
+    case K1_BF16_V7: {
+        GradV4Args g = v4_args(c, A, St, doA, doS);
+        g.prof = c->k1prof;
+        g.W = c->W; g.ldW = c->ldW;
+        if (c->k1 == K1_F16_V8) {
+            v4_f16_args(c, g, 64);
+            // its producers fetch Y (and W) eight bytes at a time: even pitch, 8-byte-aligned base, W at Y's pitch (its per-lane offsets);
+            // anything else runs k_grad_bf16_v7 on the same frame
+            c->k1_pairs = (c->ldY % 2) == 0 && (((uintptr_t)c->Y) & 7) == 0 && (c->W == nullptr || (c->ldW == c->ldY && (((uintptr_t)c->W) & 7) == 0));
+            inst = k1_instance(c->k1, c->f16_r3, c->W != nullptr, grad, c->k1_pairs);
+        }
+        if (c->chainL > 0) rc = chain_arm(c, g);     // k_grad_f16_v8<.., CHAIN> / k_grad_bf16_v7<.., CHAIN>
+        const bool v8 = c->k1 == K1_F16_V8 && inst != K1_V7;
+        if (rc == PMX_OK) rc = k1_timed(c, [&] { return v8 ? grad_launch_f16_v8(g, inst, c->stream) : grad_launch_bf16_v7(g, c->stream); });
+        break;
+    }
+    case K1_BF16: {
         PresplitArgs ps{};
         ps.X[0] = A; ps.X[1] = St;
         for (int j = 0; j < 2; ++j) { ps.Xp[j] = c->Bp[j]; ps.Xt[j] = c->Bt[j]; ps.rows[j] = c->rowsK[j]; ps.rowsPad[j] = c->rowsPad[j]; }
-        ps.K = (int)Kq; ps.KP = c->KP;
+        ps.K = (int)c->Kk; ps.KP = c->KP;
         ps.status = c->dstatus;
-        if (!grad_bf16_reads_fp32(c->plan, c->Mk, c->Nk, Kq)) launch_presplit(ps, c->stream);
+        launch_presplit(ps, c->stream);
         GradBfArgs g{};
         g.Y = c->Y; g.ldY = c->ldY;
         g.Ap = c->Bp[0]; g.At = c->Bt[0]; g.Sp = c->Bp[1]; g.Stt = c->Bt[1];
@@ -1235,66 +1283,37 @@ static int enqueue_grad_once(pmx_ctx* c, const float* A, const float* St, int do
         g.slabA = c->slab[0]; g.slabS = c->slab[1];
         g.lossPart = c->lossPart;
         g.status = c->dstatus;
-        g.M = (int)c->Mk; g.N = (int)c->Nk; g.K = (int)Kq;
+        g.M = (int)c->Mk; g.N = (int)c->Nk; g.K = (int)c->Kk;
         g.RP = c->plan.RP;
         g.doA = doA; g.doS = doS;
         g.prof = c->k1prof;
         g.W = c->W; g.ldW = c->ldW;
-        if (c->use_f16) {   // operand scales of the two-term fp16 kernel: maxima of THESE factor arrays
-            AbsmaxArgs am{};
-            am.X[0] = A; am.X[1] = St;
-            am.count[0] = c->M * Kq; am.count[1] = c->N * Kq;
-            am.out = c->absmax;
-            am.status = c->dstatus;
-            if (!absmax_fresh) launch_absmax(am, c->stream);
-            g.absmax = c->absmax; g.ymax = c->ymax; g.wmax = c->wmax;
-            g.wstatus = c->dstatus; g.rangeRatio = c->rangeRatio; g.r3 = c->f16_r3; g.consPrio = k1_prio_for(c, 64);
-        }
-        if (c->chainL > 0) {                 // k_grad_f16_v8<.., CHAIN> / k_grad_bf16_v7<.., CHAIN>
-            if (c->chainSeq >= (1u << 21)) {   // arrival words would run out of bits: start over
-                HIP_CHECK(hipMemsetAsync(c->chainFlags, 0, (size_t)(c->plan.gridX * c->plan.gridY / c->chainL) * c->plan.RP * 4 * sizeof(unsigned), c->stream));
-                c->chainSeq = 0;
-            }
-            g.chainL = c->chainL; g.chainFlags = c->chainFlags; g.chainBase = (++c->chainSeq) * 64u; g.wstatus = c->dstatus;
-            g.chainInject = c->hook_inject_k1 > 0 && (int)c->chainSeq == c->hook_inject_k1;   // tests (read once, at pmx_ctx_create)
-        }
-        if (timed) HIP_CHECK(hipEventRecord(c->ev[c->ev_used], c->stream));
-        bool took_f16 = false;
-        HIP_CHECK(grad_launch_bf16(c->plan, g, A, St, c->stream, &c->nloss, &took_f16));
-        c->f16_fell_back = c->use_f16 && !took_f16;      // (pmx_k1_info reports the kernel that ran)
-        if ((doA & 1) || doS) fix_pending = c->use_f16 && took_f16 && c->f16_r3 == 2 && c->W == nullptr && c->fixPart != nullptr;   // (grad_launch_f16_v8's own test)
-    } else {
+        rc = k1_timed(c, [&] { return grad_launch_bf16(c->plan, g, c->stream); });
+        break;
+    }
+    default: {                             // K1_SMALL, K1_F32, K1_F32PC
         GradArgs g = small_grad_args(c, A, St, doA, doS);
-        if (c->f32pc && !c->use_small) { g.fold = c->k1_fold; c->k1_fold = K1GramFold{}; }     // (k_grad_f32_pc carries the fold; pgm_enqueue_iteration arms it for that kernel only)
-        if (timed) HIP_CHECK(hipEventRecord(c->ev[c->ev_used], c->stream));
-        if (c->f32pc && c->chainL > 0) {
-            if (c->chainSeq >= (1u << 21)) {   // arrival words would run out of bits: start over
-                HIP_CHECK(hipMemsetAsync(c->chainFlags, 0, (size_t)(c->plan.gridX * c->plan.gridY / c->chainL) * c->plan.RP * 4 * sizeof(unsigned), c->stream));
-                c->chainSeq = 0;
-            }
-            GradArgs gc = g;
-            gc.chainL = c->chainL; gc.chainFlags = c->chainFlags; gc.chainBase = (++c->chainSeq) * 64u; gc.wstatus = c->dstatus;
-            gc.chainInject = c->hook_inject_k1 > 0 && (int)c->chainSeq == c->hook_inject_k1;   // tests (read once, at pmx_ctx_create)
-            HIP_CHECK(grad_launch_f32pc(c->plan, gc, c->stream));
-        } else
-        HIP_CHECK(c->use_small ? grad_launch_small(c->plan, g, c->stream) : (c->f32pc ? grad_launch_f32pc(c->plan, g, c->stream) : grad_launch_f32(c->plan, g, c->stream)));
-        c->nloss = c->plan.gridX * c->plan.gridY;
+        if (c->k1 == K1_F32PC) {
+            g.fold = fold;
+            if (c->chainL > 0) rc = chain_arm(c, g);     // k_grad_f32_pc<.., CHAIN>
+        }
+        if (rc == PMX_OK)
+            rc = k1_timed(c, [&] { return k1_small(c->k1) ? grad_launch_small(c->plan, g, c->stream) : c->k1 == K1_F32PC ? grad_launch_f32pc(c->plan, g, c->stream) : grad_launch_f32(c->plan, g, c->stream); });
+        break;
     }
-    if (timed) {
-        HIP_CHECK(hipEventRecord(c->ev[c->ev_used + 1], c->stream));
-        c->ev_used += 2;
     }
-    if ((doA & 1) || doS) c->fix_on = fix_pending;
+    if (rc != PMX_OK) return rc;
+    if (grad) c->fix_on = inst == K1_HH;
     // what the high x high residual left out, as one more slab per block (k_gfix.hip).  In the launch stream: the three launches depend on the
     // factors only, but nothing fits BESIDE K1 (its waves hold all 512 registers of every SIMD) -- measured on a stream of their own they sat
     // behind K1's workgroups and the pass got 2 % slower (profiles/r05_a_gfix_side_stream.txt)
-    if (fix_pending) { const int rcf = enqueue_gfix(c, A, St, doA, doS, c->stream); if (rcf != PMX_OK) return rcf; }
+    if (inst == K1_HH) return enqueue_gfix(c, A, St, doA, doS, c->stream);
     return PMX_OK;
 }
 
 static int enqueue_grad(pmx_ctx* c, const float* A, const float* St, int doA, int doS, bool absmax_fresh = false) {
     int rc = enqueue_grad_once(c, A, St, doA, doS, absmax_fresh);
-    if (rc != PMX_OK || !c->k1_sync_check || !c->f16_scales || c->host_grad || !(doA | doS)) return rc;
+    if (rc != PMX_OK || !c->k1_sync_check || !k1_fp16(c->k1) || c->host_grad || !(doA | doS)) return rc;
     // a path with nothing to repeat an iteration into: the fp16 kernel's range guard (f16_range_fault) is looked at NOW, with nothing
     // behind the launch yet -- refused: the context leaves the fp16 kernels and the same gradient pass runs in exact fp32
     rc = read_status(c);
@@ -1677,7 +1696,7 @@ extern "C" int pmx_grad(pmx_ctx* c) {
         f.status = c->dstatus;
         launch_fold(f, 2, c->stream);
         HIP_CHECK(hipGetLastError());
-        if (c->chainL == 0 && !c->f16_scales) { HIP_CHECK(hipStreamSynchronize(c->stream)); break; }
+        if (c->chainL == 0 && !k1_fp16(c->k1)) { HIP_CHECK(hipStreamSynchronize(c->stream)); break; }
         rc = read_status(c);
         if (rc != PMX_OK) return rc;
         int again = 0;
@@ -2022,7 +2041,7 @@ static int pgm_enqueue_iteration(pmx_ctx* c) {
     const float* A = p.accelerated ? c->Xe[0] : c->X[0];
     const float* St = p.accelerated ? c->Xe[1] : c->X[1];
     int rc;
-    if (c->use_small && eig_small_applies(c) && !p.use_fixed_steps && !p.bb_type && !(getenv("PMX_SMALL_FRONT") && atoi(getenv("PMX_SMALL_FRONT")) == 0)) {
+    if (k1_small(c->k1) && eig_small_applies(c) && !p.use_fixed_steps && !p.bb_type && !(getenv("PMX_SMALL_FRONT") && atoi(getenv("PMX_SMALL_FRONT")) == 0)) {
         rc = enqueue_small_front(c, A, St, (double)p.step_scale);          // algorithms.py:105-106, one launch
         if (rc != PMX_OK) return rc;
     } else {
@@ -2030,7 +2049,7 @@ static int pgm_enqueue_iteration(pmx_ctx* c) {
         // K = 32 (cfg2's: k_grad_f16_k32, k_grad_f32_pc<32>), their fold (and the previous iteration's stopping test) ride in K1's first workgroups and
         // k_eig follows K1: three launches per iteration instead of four (k_gram_reduce was 5.5 us of cfg2's 50; pmx_common.h: k1_gram_fold).
         const bool fold_here = !p.use_fixed_steps && !p.bb_type && c->gram_by_update && c->fold_in_k1 && !c->host_grad && !eig_small_applies(c) && c->KP == 32 && c->Kk == 32 &&
-                               (c->k32f16 || (c->f32pc && !c->use_small && !c->use_bf16)) && !c->bsd_decide_pending &&
+                               k1_carries_fold(c->k1) && !c->bsd_decide_pending &&
                                c->plan.gridX * c->plan.gridY >= k1_gram_fold_wgs(c->KP, 512);
         if (fold_here) {
             K1GramFold gf{};
@@ -2047,16 +2066,6 @@ static int pgm_enqueue_iteration(pmx_ctx* c) {
         rc = enqueue_grad(c, A, St, 1, 1, c->absmax_by_finish);               // algorithms.py:105
         if (rc != PMX_OK) return rc;
         if (fold_here) {
-            if (c->k1_fold.part != nullptr) {    // the launch that ran is not one that carries the fold (a fall-back inside enqueue_grad): the stand-alone kernel, behind K1
-                GramReduceArgs r{};
-                r.part = c->k1_fold.part; r.G = c->gramG; r.KP = c->KP; r.status = c->dstatus;
-                r.want[0] = r.want[1] = 1;
-                r.nparts[0] = c->k1_fold.nparts[0]; r.nparts[1] = c->k1_fold.nparts[1];
-                r.dec_partials = c->k1_fold.dec_partials; r.dec_status = c->k1_fold.dec_status;
-                r.dec_e_rel[0] = c->k1_fold.dec_e_rel[0]; r.dec_e_rel[1] = c->k1_fold.dec_e_rel[1];
-                c->k1_fold = K1GramFold{};
-                launch_gram_reduce(r, c->stream);
-            }
             rc = enqueue_eig_only(c, true, true, (double)p.step_scale);     // algorithms.py:106, behind K1: the update kernel is its only reader
             if (rc != PMX_OK) return rc;
         }
@@ -2109,11 +2118,11 @@ static int pgm_enqueue_iteration(pmx_ctx* c) {
         }
     }
     // the fp16 K1's operand maxima for the next iteration come from this kernel (every workgroup writes its partial: full grid only)
-    u.absmax_out = c->f16_scales ? c->absmax : nullptr;       // ([r4] any grid: the workgroups that exist zero the slots of those that do not)
+    u.absmax_out = k1_fp16(c->k1) ? c->absmax : nullptr;       // ([r4] any grid: the workgroups that exist zero the slots of those that do not)
     u.e_rel[0] = p.e_rel[0]; u.e_rel[1] = p.e_rel[1];
     // the next iteration's partial Gram matrices from this launch (PgmArgs::gramPart): the Lipschitz rule on factors of <= 4096
     // rows each, K <= 64 (cfg2); PMX_GRAM_IN_UPDATE=0 keeps k_gram_partial (A/B)
-    const bool gram_here = !p.use_fixed_steps && !p.bb_type && !c->use_small && c->K <= 64 && c->rows[0] <= 4096 && c->rows[1] <= 4096 && c->gram_in_update;
+    const bool gram_here = !p.use_fixed_steps && !p.bb_type && !k1_small(c->k1) && c->K <= 64 && c->rows[0] <= 4096 && c->rows[1] <= 4096 && c->gram_in_update;
     u.gramPart = gram_here ? c->gramPart : nullptr;
     u.KP = c->KP;
     launch_pgm_update(u, c->stream);                                      // algorithms.py:107-108
@@ -2628,7 +2637,7 @@ static int ada_enqueue_tail(pmx_ctx* c, int t) {
     f.colpart = c->colpart;
     f.check_convergence = p.check_convergence;
     static_assert(EW_BLOCKS == 256, "k_grad_f16_v8 folds 256 partial maxima per factor");
-    f.absmax_out = c->f16_scales ? c->absmax : nullptr;
+    f.absmax_out = k1_fp16(c->k1) ? c->absmax : nullptr;
     launch_ada_finish(f, c->stream);
     AdaDecideArgs d{};
     d.al = alpha_args(c);
@@ -2701,7 +2710,7 @@ static int ada_enqueue_tail_fused(pmx_ctx* c, int it, double b1t, double b1prev)
     m.check_convergence = p.check_convergence;
     t.prox_max_iter = p.prox_max_iter;
     t.colpart = c->colpart;
-    t.absmax_out = c->f16_scales ? c->absmax : nullptr;
+    t.absmax_out = k1_fp16(c->k1) ? c->absmax : nullptr;
     t.al = alpha_args(c);
     t.al.use_fixed = p.use_fixed_steps;
     t.al.fixed[0] = (float)p.fixed_alpha[0];
@@ -3113,7 +3122,7 @@ static int bsdmm_enqueue_iteration(pmx_ctx* c) {
         u.status = c->dstatus;
         u.partials = c->partials;
         // this block's maxima for the fp16 K1 (the other block's are still those of the launch that last wrote it)
-        u.absmax_out = c->f16_scales ? c->absmax : nullptr;
+        u.absmax_out = k1_fp16(c->k1) ? c->absmax : nullptr;
         launch_bsdmm_update(u, c->stream);
         c->absmax_by_finish = u.absmax_out != nullptr;
         BsdmmDecideArgs d{};
