@@ -53,6 +53,8 @@ def apply_prox(X, step, spec):
     if spec is None:
         return np.array(X, copy=True)
     name = spec[0]
+    if name == "seq":                                  # ("seq", [specs], repeat): AlternatingProjections as a prox spec
+        return apply_prox_sequence(X, step, spec[1], spec[2] if len(spec) > 2 else 1)
     if name == "id":                                   # operators.py:20-23
         return np.array(X, copy=True)
     if name == "zero":                                 # operators.py:26-30
@@ -190,7 +192,7 @@ def _sumsq(x):
 
 
 def pgm_nmf(Y, A, S, prox_A=("plus",), prox_S=("plus",), step=None, accelerated=False,
-            backtracking=False, max_iter=1000, e_rel=1e-3, callback=None, trace=None, W=None):
+            backtracking=False, max_iter=1000, e_rel=1e-3, callback=None, trace=None, W=None, grad=None):
     """`nmf(Y, A, S, algorithm=pgm, ...)` (nmf.py:150-162 -> algorithms.py:12-144).
 
     A and S are updated in place.  `step`: None -> lipschitz_steps evaluated at the
@@ -199,6 +201,8 @@ def pgm_nmf(Y, A, S, prox_A=("plus",), prox_S=("plus",), step=None, accelerated=
     the first three (algorithms.py:144); n_iter is what it logs (:140).
     `trace`, if a list, receives (A.copy(), S.copy()) BEFORE each update, i.e. what the
     reference's callback sees (algorithms.py:90).
+    `grad`: None -> the NMF likelihood gradient of Y; or a callable (E0, E1) -> (gA, gS), the reference's
+    `grads = grad(*_X)` (algorithms.py:105) for any other smooth function (Y may then be None).
     """
     X = [A, S]
     specs = [prox_A, prox_S]
@@ -225,7 +229,7 @@ def pgm_nmf(Y, A, S, prox_A=("plus",), prox_S=("plus",), step=None, accelerated=
         else:
             E = [X[j].copy() for j in range(2)]                        # :96-99 (alias/copy)
         prev = [x.copy() for x in X]                                   # :102
-        G = residual_gradients(E[0], E[1], Y, W)                       # :105
+        G = residual_gradients(E[0], E[1], Y, W) if grad is None else tuple(grad(E[0], E[1]))   # :105
         if step is None and W is not None:
             # nmf.step_pgm tests `W == 1` on the array (nmf.py:63): NumPy raises, and so does the reference
             raise ValueError("The truth value of an array with more than one element is ambiguous. Use a.any() or a.all()")
@@ -305,14 +309,16 @@ def moment_update(scheme, it, G, M, V, Vhat, b1, b2, eps, p):
 def adaprox_nmf(Y, A, S, prox_A=("plus",), prox_S=("plus",), step=None, scheme="adam",
                 b1=0.9, b2=0.999, eps=1e-8, check_convergence=True, p=0.25, max_iter=1000,
                 e_rel=1e-3, prox_max_iter=1000, M=None, V=None, Vhat=None, callback=None,
-                trace=None, W=None, sub_trace=False):
+                trace=None, W=None, sub_trace=False, grad=None):
     """`nmf(Y, A, S, algorithm=adaprox, ...)` (nmf.py:164-176 -> algorithms.py:248-423).
     sub_trace=True appends a seventh return value: the proximal pass counts [tau_A, tau_S] of every iteration
     (bench.py compares them with the device's over the same iteration window).
 
     Returns (converged, M, V, Vhat, n_iter, sub_iters) -- the reference returns the first
     four (:423) and logs the last two (:415-417).  prox spec None skips the sub-iteration
-    loop entirely (:380)."""
+    loop entirely (:380).
+    `grad`: None -> the NMF likelihood gradient of Y; or a callable (A, S) -> (gA, gS), the reference's
+    `G = grad(*X)` (:369) for any other smooth function (Y may then be None)."""
     X = [A, S]
     specs = [prox_A, prox_S]
     e = (e_rel, e_rel) if np.isscalar(e_rel) else tuple(e_rel)
@@ -341,7 +347,7 @@ def adaprox_nmf(Y, A, S, prox_A=("plus",), prox_S=("plus",), step=None, scheme="
                 callback(A, S, it=it)
             except StopIteration:
                 break
-        G = residual_gradients(A, S, Y, W)                             # :369 (Jacobi: both at old X)
+        G = residual_gradients(A, S, Y, W) if grad is None else tuple(grad(A, S))   # :369 (Jacobi: both at old X)
         alpha = adaprox_steps(A, S) if step is None else tuple(step(A, S, it))   # :370
         prev = [x.copy() for x in X] if check_convergence else None   # :371-372
         for j in range(2):
