@@ -99,7 +99,10 @@ enum {
 
 /* One proximal operator.  `unit` says which sum prox_unity* normalises by, in DEVICE layout:
  * 0 = along the K components of one row (numpy axis=1 for A, axis=0 for S),
- * 1 = along the rows, per component     (numpy axis=0 for A, axis=1 for S).
+ * 1 = along the rows, per component     (numpy axis=0 for A, axis=1 for S): a sum over the whole factor per application.
+ *     Taken by the stand-alone operator entry points (pmx_prox_apply / pmx_prox_array) and by pmx_pgm_begin -- pgm / FISTA
+ *     with any of its step rules, no line search, no host_prox, not in fp64 or row-sharded contexts: the update then runs as
+ *     a chain of 1 + (applications per iteration) launches.  Every other solver entry point answers PMX_E_UNSUPPORTED.
  * `relative` = 1 is the reference's type="relative" (threshold multiplied by the step the
  * solver passes to the prox, operators.py:4-14), 0 is type="absolute". */
 typedef struct pmx_prox {

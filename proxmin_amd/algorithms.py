@@ -11,7 +11,10 @@ chains.  ANY OTHER Python callable keeps the reference's contract -- `prox(X, st
 (algorithms.py:37-39), `step(*X, it=None[, grads=None])` (:73-77, :370) -- through a host round trip:
 one iteration per call, the callable's arguments copied to the host ((M + N) K floats), its result
 copied back, everything else (gradient, update, norms, built-in operators) still on the device.  A
-one-time warning says so.  A user `grad(*X) -> (gA, gS)` callable (any differentiable function of the two factors,
+one-time warning says so.  prox_unity / prox_unity_plus along a factor's LONG axis (axis=0 on A, axis=1 on S: a sum over the
+whole factor per application) are fused in pgm / FISTA -- the update becomes a chain of launches, one more per application
+(csrc/k_update.hip: k_pgm_unity) -- unless the call has a line search or a user grad / step / prox; there, and in adaprox and
+bsdmm, they take the host road too (the stand-alone device operator between kernel launches).  A user `grad(*X) -> (gA, gS)` callable (any differentiable function of the two factors,
 algorithms.py:12,248) takes the same road: the point is copied to the host, the callable's result into the device's gradient
 buffers, and the update runs on the device (pgm and adaprox; no Y is needed then).  bsdmm: user-defined members of `proxs_g`
 and user-defined `prox_A` / `prox_S` are applied between the pieces of a block update (pmx_bsdmm_split); generic, untagged
@@ -150,12 +153,22 @@ def _warn_host_path(what):
                        "the whole iteration on the GPU" % what)
 
 
-def _split_prox(prox, none_is_id):
+def _warn_long_axis(j, exc):
+    if "unity-long-%d" % j not in _warned:
+        _warned.add("unity-long-%d" % j)
+        logger.warning("proxmin_amd: %s: one iteration per call, its argument goes through the host" % exc)
+
+
+def _split_prox(prox, none_is_id, long_axis=None):
     """-> (device operator sequences, [callable or None per block]): operators of this library become device sequences,
-    anything else is kept for the host round trip (its device slot is prox_id / no operator)."""
+    anything else is kept for the host round trip (its device slot is prox_id / no operator).  long_axis: a list (pgm) that
+    receives, per block, None or (sequence with its long-axis prox_unity* entries, the NotFusable raised for it); the
+    warning for such a block is then left to the caller, who may still keep the sequence on the device (_fuse_long_axis)."""
     seqs, host = [], []
     for j, p in enumerate(prox):
         q = operators.prox_id if (p is None and none_is_id) else p
+        if long_axis is not None:
+            long_axis.append(None)
         try:
             seqs.append(operators.device_proxseq(q, j, for_solver=True))
             host.append(None)
@@ -163,14 +176,33 @@ def _split_prox(prox, none_is_id):
             if not callable(q):
                 raise
             if isinstance(exc, operators.NotFusable):
-                if "unity-long-%d" % j not in _warned:
-                    _warned.add("unity-long-%d" % j)
-                    logger.warning("proxmin_amd: %s: one iteration per call, its argument goes through the host" % exc)
+                if long_axis is not None:
+                    long_axis[j] = (operators.device_proxseq(q, j, for_solver="pgm"), exc)
+                else:
+                    _warn_long_axis(j, exc)
             else:
                 _warn_host_path("prox of block %d (%r)" % (j, q))
             seqs.append(operators.device_proxseq(operators.prox_id if none_is_id else None, j))
             host.append(q)
     return seqs, host
+
+
+def _fuse_long_axis(seqs, host_prox, long_axis, host_route):
+    """pgm: sequences with prox_unity* along the long axis stay on the device (k_pgm_unity's chain) unless something else of
+    the call needs the host (`host_route`: a user grad / step, the line search) or another block's prox is a user
+    callable; then they take the host route of a user prox, with its one-time warning.  In place; -> fused or not."""
+    if not any(long_axis):
+        return False
+    other_host = any(h is not None and long_axis[j] is None for j, h in enumerate(host_prox))
+    if host_route or other_host:
+        for j, la in enumerate(long_axis):
+            if la is not None:
+                _warn_long_axis(j, la[1])
+        return False
+    for j, la in enumerate(long_axis):
+        if la is not None:
+            seqs[j], host_prox[j] = la[0], None
+    return True
 
 
 def _user_steps(s, what, shapes):
@@ -223,7 +255,8 @@ def pgm(X, grad, step, prox=None, accelerated=False, backtracking=False, f=None,
     Y, A, S, W = _problem_from_grad(X, grad)
     prox = _prox_pair(prox)
     # prox=None means prox_id in pgm (algorithms.py:63-64)
-    seqs, host_prox = _split_prox(prox, none_is_id=True)
+    long_axis = []
+    seqs, host_prox = _split_prox(prox, none_is_id=True, long_axis=long_axis)
     e_rel = _e_rel_pair(e_rel)
     user_grad = Y is None
     assert backtracking is False or f is not None
@@ -259,6 +292,8 @@ def pgm(X, grad, step, prox=None, accelerated=False, backtracking=False, f=None,
         _warn_host_path("step (%r)" % (step,))
     else:
         raise TypeError("step must be callable")
+    # prox_unity* along a factor's long axis: on the device (one more launch per application) when nothing else needs the host
+    fused_long = _fuse_long_axis(seqs, host_prox, long_axis, host_route=user_step is not None or user_grad or bool(backtracking))
     slow = user_step is not None or any(h is not None for h in host_prox) or user_grad
     # a user `step` next to the line search: the callable on the host once per iteration, the Beck-Teboulle loop on the device
     bt_user_step = backtracking and user_step is not None and not any(h is not None for h in host_prox) and not user_grad
@@ -275,7 +310,7 @@ def pgm(X, grad, step, prox=None, accelerated=False, backtracking=False, f=None,
     # [r4] fp64 inputs of a small problem, everything of the iteration on the device: fp64 arithmetic (PMX_MODE_F64)
     from .engine import f64_applies
     # [r6] ... at any size up to K = 128, weighted or not, with the Beck-Teboulle line search (the matrix-core kernels: k_big_f64.hip)
-    f64 = (not slow and bb is None and Y is not None and not isinstance(W, DeviceArrayRef)
+    f64 = (not slow and not fused_long and bb is None and Y is not None and not isinstance(W, DeviceArrayRef)
            and all(x.dtype == np.float64 for x in (Y, A, S)) and f64_applies(A.shape[0], S.shape[1], A.shape[1], weighted=W is not None or backtracking))
     with _open_device(Y, A, S, W, f64=f64, f64_mfma=backtracking) as dev:
         dev.pgm_begin(seqs, accelerated=accelerated, step_scale=scale, fixed_steps=(1.0, 1.0) if user_step is not None else fixed,

@@ -1006,6 +1006,172 @@ __global__ __launch_bounds__(EW_THREADS) void k_colscale(ColScaleArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// PGM / FISTA update whose operator sequence holds prox_unity* ALONG THE ROWS (pmx_prox::unit != 0: numpy axis = 0 on A,
+// axis = 1 on S).  Every such application needs the column sums of the whole factor, so it costs one launch boundary: the
+// sequence, unrolled over `repeat`, is cut at these entries into within-row segments  seg_0, U_1, seg_1, ..., U_L, seg_L  and
+// the update runs as a chain of L + 1 launches of this kernel (pmx_api.hip: launch_pgm_unity_chain):
+//   head    v = Xe - s G (k_pgm_update's expression), seg_0, the `plus` of a unity_plus; v into the block's scratch array T, G
+//           to its output, the workgroup's column sums of v through colsum_store into `wr`;
+//   middle  (L > 1) the previous sums folded by colsum_fold, the division, the next segment, new sums into the other half
+//           of the partials (a workgroup may still be folding the previous ones);
+//   finish  fold, division, seg_L and then all that k_pgm_update does behind its prox_row.
+// Per-thread float sums in row order and the double fold are k_colsum's / k_colscale's: the result is bit for bit what the
+// stand-alone operator gives on the same argument.  No zero guard (a column that sums to zero becomes NaN, like the
+// reference's); only components < K are divided.  A block without such an entry is updated whole in the finish launch; a
+// block with fewer applications than the other idles in the middle launches it does not need.
+// ------------------------------------------------------------------------------------------------
+struct PgmUnityBlock {
+    int act;             // the block takes part in this launch
+    int first;           // v = Xe - s G from the gradient slabs (and G is written); else v is read from T
+    int div;             // the launch opens with the division by the column sums folded from `rd`
+    int p0, p1;          // entries [p0, p1) of the unrolled sequence (entry p is seq[p % n]) are applied to every row
+    int sum;             // 0: none (finish); 1: the column sums of the result go to `wr`; 2: after the `plus` of a unity_plus
+    const double* rd;    // [2][EW_BLOCKS][MAXK]
+    double* wr;          // [2][EW_BLOCKS][MAXK]
+};
+struct PgmUnityArgs {
+    PgmArgs u;           // (mode, stepArr unused; T[j]: block j's scratch array, rows x K)
+    PgmUnityBlock b[2];
+    int finish;
+};
+template <int NC>
+__global__ __launch_bounds__(EW_THREADS) void k_pgm_unity(PgmUnityArgs aa) {
+    __shared__ double scratch[2 * EW_WAVES];
+    __shared__ int s_last;
+    __shared__ float gtile[NC <= 2 ? 32 : 1][NC <= 2 ? 32 * NC + 1 : 1];
+    __shared__ double asum[ALPHA_NG][MAXK];
+    __shared__ float tot[MAXK];
+    __shared__ float sm[(EW_THREADS / 32) * MAXK];
+    const PgmArgs& a = aa.u;
+    const int j = blockIdx.y;
+    const int halted = __builtin_nontemporal_load(&a.status->halt);
+    const float s = (float)a.status->step[j];
+    if (halted) return;
+    const PgmUnityBlock& ub = aa.b[j];
+    if (!ub.act) return;
+    const bool finish = aa.finish != 0;
+    const int64_t rows = a.rows[j];
+    const int K = a.K;
+    const ProxSeq& px = a.prox[j];
+    float* X = a.X[j];
+    float* Xe = a.Xe[j];
+    float* T = a.T[j];
+    if (ub.div) {                            // k_colscale's fold: the float totals of the previous application
+        colsum_fold(ub.rd + (int64_t)j * EW_BLOCKS * MAXK, K, false, asum);
+        if (threadIdx.x < MAXK) {
+            double t = 0.0;
+            for (int q = 0; q < ALPHA_NG; ++q) t += asum[q][threadIdx.x];
+            tot[threadIdx.x] = (float)t;
+        }
+        __syncthreads();
+    }
+    float cs[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) cs[c] = 0.f;
+    float d2 = 0.f, n2 = 0.f, xmax = 0.f;
+    ROW_LOOP_BEGIN(rows)
+        bool ok[NC];
+        float g[NC], xo[NC], v[NC], sk[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) ok[c] = l32 + 32 * c < K;
+        if (ub.first) load_grad<NC>(g, ok, a.slab[j], rows, K, r, l32);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int64_t e = r * K + l32 + 32 * c;
+            xo[c] = (ok[c] && (ub.first || finish)) ? X[e] : 0.f;
+            if (ub.first) {
+                const float xe = a.accelerated ? (ok[c] ? Xe[e] : 0.f) : xo[c];
+                v[c] = xe - s * g[c];
+            } else {
+                v[c] = ok[c] ? T[e] : 0.f;
+            }
+            if (ub.div && ok[c]) v[c] = v[c] / tot[l32 + 32 * c];
+            sk[c] = s;
+        }
+        for (int p = ub.p0; p < ub.p1; ++p) prox_one<NC>(v, ok, px.seq[p % px.n], sk);
+        if (!finish) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                if (ub.sum == 2) v[c] = v[c] < 0.f ? 0.f : v[c];            // plus first (operators.py:48-52)
+                if (ok[c]) {
+                    const int64_t e = r * K + l32 + 32 * c;
+                    T[e] = v[c];
+                    if (ub.first) a.G[j][e] = g[c];
+                    cs[c] += v[c];
+                }
+            }
+            continue;
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            if (ok[c]) {
+                const int64_t e = r * K + l32 + 32 * c;
+                X[e] = v[c];
+                if (ub.first) a.G[j][e] = g[c];
+                float xnext = v[c];          // the point the next gradient is evaluated at
+                if (a.accelerated) { xnext = v[c] + a.omega_next * (v[c] - xo[c]); Xe[e] = xnext; }
+                if constexpr (NC <= 2) { if (a.gramPart != nullptr) gtile[threadIdx.x >> 5][l32 + 32 * c] = xnext; }
+                xmax = fmaxf(xmax, fabsf(xnext));
+                const float d = v[c] - xo[c];
+                d2 += d * d;
+                n2 += v[c] * v[c];
+            }
+        }
+    ROW_LOOP_END
+    if (!finish) {
+        double* wr = ub.wr;
+        colsum_store<NC>(cs, wr, j, sm);
+        if (threadIdx.x < 32 * NC)           // (a grid of nbx < EW_BLOCKS: colsum_fold reads every slot)
+            for (int b = blockIdx.x + gridDim.x; b < EW_BLOCKS; b += gridDim.x) wr[((int64_t)j * EW_BLOCKS + b) * MAXK + threadIdx.x] = 0.0;
+        return;
+    }
+    // from here on: k_pgm_update's tail (Gram side output, operand maxima, the sums of the stopping test, the test)
+    if constexpr (NC <= 2) {
+        if (a.gramPart != nullptr) {
+            const int KP = a.KP;
+            const int64_t row0 = (int64_t)blockIdx.x * (EW_THREADS / 32);
+            const int nrow = rows - row0 < EW_THREADS / 32 ? (int)(rows - row0) : EW_THREADS / 32;
+            __syncthreads();
+            float* out = a.gramPart + ((int64_t)j * GRAM_BLOCKS + blockIdx.x) * KP * KP;
+            for (int e = threadIdx.x; e < KP * KP; e += EW_THREADS) {
+                const int gi = e / KP, gj = e - gi * KP;
+                float acc = 0.f;
+                if (gi < K && gj < K)
+                    for (int rr = 0; rr < nrow; ++rr) acc += gtile[rr][gi] * gtile[rr][gj];
+                out[e] = acc;
+            }
+            __syncthreads();
+        }
+    }
+    if (a.absmax_out != nullptr) {
+        const double m = wave_max((double)xmax);
+        if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = m;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double mm = scratch[0];
+            for (int q = 1; q < EW_WAVES; ++q) mm = fmax(mm, scratch[q]);
+            a.absmax_out[j * EW_BLOCKS + blockIdx.x] = (float)mm;
+            for (int b = blockIdx.x + gridDim.x; b < EW_BLOCKS; b += gridDim.x) a.absmax_out[j * EW_BLOCKS + b] = 0.f;
+        }
+        __syncthreads();
+    }
+    double red[2] = {(double)d2, (double)n2};
+    if (a.tickets == nullptr) {
+        block_sum_store<2>(red, part_ptr(a.partials, SL_DIFF2, j) + blockIdx.x, (int64_t)2 * EW_BLOCKS, scratch);
+        return;
+    }
+    block_sum_store_wt<2>(red, part_ptr(a.partials, SL_DIFF2, j) + blockIdx.x, (int64_t)2 * EW_BLOCKS, scratch);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned old = __hip_atomic_fetch_add(a.tickets, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = old == a.ticket_last;
+    }
+    __syncthreads();
+    if (s_last) pgm_decide_body(a.status, a.partials, a.e_rel, 1, true);
+}
+
+// ------------------------------------------------------------------------------------------------
 // adaprox: moments + update                      (proxmin/algorithms.py:147-245, :369-378)
 // ------------------------------------------------------------------------------------------------
 struct MomentArgs {
@@ -2572,6 +2738,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_shard_post_split(ShardPostSplitA
 void launch_fold(const FoldArgs& a, int nblocks_y, hipStream_t s) { DISPATCH_NC(a.K, k_fold, dim3(EW_BLOCKS, nblocks_y), s, a); }
 void launch_prox_apply(const ProxArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_prox_apply, dim3(EW_BLOCKS), s, a); }
 void launch_pgm_update(const PgmArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_pgm_update, dim3(a.nbx > 0 ? a.nbx : EW_BLOCKS, 2), s, a); }
+void launch_pgm_unity(const PgmUnityArgs& a, hipStream_t s) { DISPATCH_NC(a.u.K, k_pgm_unity, dim3(a.u.nbx > 0 ? a.u.nbx : EW_BLOCKS, 2), s, a); }
 void launch_bb_reduce(const BBArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_bb_reduce, dim3(EW_BLOCKS, 2), s, a); }
 void launch_bb_step(const BBStepArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_bb_step, dim3(1), dim3(EW_THREADS), 0, s, a); }
 void launch_bt_update(const BtArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_bt_update, dim3(EW_BLOCKS, 2), s, a); }

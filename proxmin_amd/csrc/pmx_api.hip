@@ -176,6 +176,8 @@ struct pmx_ctx {
     GridBar* gridbar = nullptr;            // its barrier state
     long long* tailprof = nullptr;         // PMX_TAIL_PROF=1: phase time stamps of the last fused tail
     unsigned* tickets = nullptr;           // pgm: arrival counter of the update kernel's last-workgroup stopping test
+    bool pgm_long = false;                 // pgm: an operator sequence holds prox_unity* along the rows: the update is k_pgm_unity's chain (Xp[j]: block j's scratch array)
+    double* unityPart = nullptr;           // its column-sum partials, two halves used in turn: [2][2][EW_BLOCKS][MAXK]
     unsigned ticketLaunches = 0;           // tickets drawn by the update launches so far
     int tailFaults = 0;
     float* slab[2] = {nullptr, nullptr};
@@ -266,17 +268,24 @@ static ProxSeq to_dev(const pmx_proxseq& p) {
     for (int i = 0; i < PMX_MAX_SEQ; ++i) d.seq[i] = p.seq[i];
     return d;
 }
-// standalone: the stand-alone operator entry points (pmx_prox_apply / pmx_prox_array), which also normalise along the rows
-static int check_prox(const pmx_proxseq& p, const char* what, bool standalone = false) {
+static bool prox_long_axis(const pmx_proxseq& p) {       // prox_unity* along the rows of the device array: a sum over the whole factor
+    for (int i = 0; i < p.n && i < PMX_MAX_SEQ; ++i)
+        if ((p.seq[i].op == PMX_PROX_UNITY || p.seq[i].op == PMX_PROX_UNITY_PLUS) && p.seq[i].unit != 0) return true;
+    return false;
+}
+// long_axis_ok: the caller has a place for prox_unity* along the rows -- the stand-alone operator entry points (pmx_prox_apply /
+// pmx_prox_array) and pmx_pgm_begin (k_pgm_unity's chain)
+static int check_prox(const pmx_proxseq& p, const char* what, bool long_axis_ok = false) {
     if (p.n < 0 || p.n > PMX_MAX_SEQ) FAIL(PMX_E_INVALID, "%s: bad operator count %d", what, p.n);
     for (int i = 0; i < p.n; ++i) {
         const pmx_prox& q = p.seq[i];
         if (q.op < PMX_PROX_ID || q.op > PMX_PROX_SOFT_PLUS) FAIL(PMX_E_INVALID, "%s: unknown prox op %d", what, q.op);
-        if ((q.op == PMX_PROX_UNITY || q.op == PMX_PROX_UNITY_PLUS) && q.unit != 0 && !standalone)
-            FAIL(PMX_E_UNSUPPORTED, "%s: prox_unity along the row dimension (numpy axis=0 on A / axis=1 on S) needs a grid-wide sum per "
-                                    "application and is not part of the fused solver kernels (the host wrappers apply it between kernel "
-                                    "launches through pmx_prox_apply)", what);
     }
+    if (prox_long_axis(p) && !long_axis_ok)
+        FAIL(PMX_E_UNSUPPORTED, "%s: prox_unity along the row dimension (numpy axis=0 on A / axis=1 on S) needs a grid-wide sum per "
+                                "application: pgm / FISTA run it inside the update chain (pmx_pgm_begin without line search, user prox, "
+                                "row sharding or fp64), every other solver entry point does not contain it (the host wrappers apply it "
+                                "between kernel launches through pmx_prox_apply)", what);
     return PMX_OK;
 }
 
@@ -1937,10 +1946,17 @@ extern "C" int pmx_pgm_begin(pmx_ctx* c, const pmx_pgm_params* p) {
     int rc = require_ready(c, true);
     if (rc != PMX_OK) return rc;
     if (!p) FAIL(PMX_E_INVALID, "params is NULL");
+    bool long_axis = false;
     for (int j = 0; j < 2; ++j) {
-        rc = check_prox(p->prox[j], j ? "prox_S" : "prox_A");
+        rc = check_prox(p->prox[j], j ? "prox_S" : "prox_A", true);
         if (rc != PMX_OK) return rc;
+        long_axis |= !p->host_prox[j] && prox_long_axis(p->prox[j]);
     }
+    if (long_axis && (p->backtracking || p->host_prox[0] || p->host_prox[1] || c->f64 || c->comm))
+        FAIL(PMX_E_UNSUPPORTED, "prox_unity along the row dimension (numpy axis=0 on A / axis=1 on S) runs inside pgm / FISTA without line search, "
+                                "without a user prox next to it, and not in fp64 or row-sharded contexts (the host wrappers apply it between kernel "
+                                "launches through pmx_prox_apply there)");
+    c->pgm_long = long_axis;
     if (c->f64) {                                // PMX_MODE_F64: plain pgm / FISTA with device operators and a device or fixed step
         if (c->Wd_on && !p->use_fixed_steps && !p->unweighted_rule)     // nmf.step_pgm with an array W raises (nmf.py:63)
             FAIL(PMX_E_INVALID, "The truth value of an array with more than one element is ambiguous. Use a.any() or a.all()");
@@ -2000,6 +2016,15 @@ extern "C" int pmx_pgm_begin(pmx_ctx* c, const pmx_pgm_params* p) {
             rc = dallocT(c, &c->Xp[j], (size_t)c->rowsK[j] * c->K, c->framed);
             if (rc != PMX_OK) return rc;
         }
+    if (long_axis) {
+        for (int j = 0; j < 2; ++j)
+            if (prox_long_axis(p->prox[j])) {
+                rc = dallocT(c, &c->Xp[j], (size_t)c->rowsK[j] * c->K, c->framed);
+                if (rc != PMX_OK) return rc;
+            }
+        rc = dallocT(c, &c->unityPart, (size_t)2 * 2 * EW_BLOCKS * MAXK);
+        if (rc != PMX_OK) return rc;
+    }
     c->btT[0] = c->btT[1] = 1.0;
     if (p->backtracking) {   // host-driven trials read device sums after every K1 pass: no room for a repeated iteration
         rc = one_iteration_per_call(c);
@@ -2034,6 +2059,54 @@ static float next_omega(pmx_ctx* c) {
     const double om = (t - 1.0) / t1;
     c->nest_t = t1;
     return (float)om;
+}
+
+// The update of a context whose operator sequences hold prox_unity* along the rows (pmx_ctx::pgm_long): the sequence of block j,
+// unrolled over `repeat`, is cut at its L_j such entries; max(L_A, L_S) + 1 launches of k_pgm_unity (k_update.hip) -- head, middles,
+// finish.  A block with fewer applications idles between its last sum and the finish launch; one without any is updated whole there.
+static void launch_pgm_unity_chain(pmx_ctx* c, const PgmArgs& u) {
+    const pmx_pgm_params& p = c->pgm;
+    PgmUnityArgs a{};
+    a.u = u;
+    int total[2], L[2], pos[2] = {0, 0}, done[2] = {0, 0};
+    for (int j = 0; j < 2; ++j) {
+        a.u.T[j] = c->Xp[j];
+        const pmx_proxseq& q = p.prox[j];
+        const int rep = q.repeat < 1 ? 1 : q.repeat;
+        int nl = 0;
+        for (int i = 0; i < q.n; ++i) nl += (q.seq[i].op == PMX_PROX_UNITY || q.seq[i].op == PMX_PROX_UNITY_PLUS) && q.seq[i].unit != 0;
+        total[j] = q.n * rep;
+        L[j] = nl * rep;
+    }
+    const int Lmax = L[0] > L[1] ? L[0] : L[1];
+    const size_t half = (size_t)2 * EW_BLOCKS * MAXK;
+    for (int i = 0; i <= Lmax; ++i) {
+        a.finish = i == Lmax;
+        for (int j = 0; j < 2; ++j) {
+            PgmUnityBlock& b = a.b[j];
+            b = PgmUnityBlock{};
+            const bool more = done[j] < L[j];                // an application of this block is still ahead
+            if (!a.finish && !more) continue;                // idle in this launch
+            const pmx_proxseq& q = p.prox[j];
+            b.act = 1;
+            b.first = done[j] == 0;
+            b.div = done[j] > 0;
+            b.rd = c->unityPart + (size_t)((done[j] + 1) & 1) * half;
+            b.p0 = pos[j];
+            if (more) {
+                int e = pos[j];
+                while (!((q.seq[e % q.n].op == PMX_PROX_UNITY || q.seq[e % q.n].op == PMX_PROX_UNITY_PLUS) && q.seq[e % q.n].unit != 0)) ++e;
+                b.p1 = e;
+                b.sum = q.seq[e % q.n].op == PMX_PROX_UNITY_PLUS ? 2 : 1;
+                b.wr = c->unityPart + (size_t)(done[j] & 1) * half;
+                pos[j] = e + 1;
+                done[j] += 1;
+            } else {
+                b.p1 = total[j];
+            }
+        }
+        launch_pgm_unity(a, c->stream);
+    }
 }
 
 static int pgm_enqueue_iteration(pmx_ctx* c) {
@@ -2125,7 +2198,8 @@ static int pgm_enqueue_iteration(pmx_ctx* c) {
     const bool gram_here = !p.use_fixed_steps && !p.bb_type && !k1_small(c->k1) && c->K <= 64 && c->rows[0] <= 4096 && c->rows[1] <= 4096 && c->gram_in_update;
     u.gramPart = gram_here ? c->gramPart : nullptr;
     u.KP = c->KP;
-    launch_pgm_update(u, c->stream);                                      // algorithms.py:107-108
+    if (c->pgm_long) launch_pgm_unity_chain(c, u);                        // (only its finish launch draws tickets)
+    else launch_pgm_update(u, c->stream);                                 // algorithms.py:107-108
     HIP_CHECK(hipGetLastError());
     c->gram_by_update = gram_here;
     c->decide_pending = defer_decide;
@@ -2370,6 +2444,7 @@ extern "C" int pmx_pgm_bt_split(pmx_ctx* c, int phase, int* need, double eff_ste
     if (rc != PMX_OK) return rc;
     if (!need || !eff_steps) FAIL(PMX_E_INVALID, "NULL argument");
     if (c->algo != ALG_PGM || !c->pgm.backtracking) FAIL(PMX_E_STATE, "pmx_pgm_begin has not been called with backtracking");
+    if (c->pgm_long) FAIL(PMX_E_UNSUPPORTED, "pmx_pgm_bt_split: prox_unity along the row dimension runs inside pmx_pgm_run only");
     if (phase != 0 && phase != 1) FAIL(PMX_E_INVALID, "bad phase %d", phase);
     const int it0 = c->hstatus->it_done;
     if (phase == 0 && c->pgm.use_fixed_steps) {
@@ -2396,6 +2471,7 @@ extern "C" int pmx_pgm_split(pmx_ctx* c, int phase, const double* steps, pmx_res
     // (phase 0 alone -- the gradient at the evaluation point, for a user `step` that wants `grads` -- is harmless next to
     //  the line search: the iteration itself then runs through pmx_pgm_run(ctx, 1) with the steps of pmx_pgm_set_fixed_steps)
     if (p.backtracking && phase != 0) FAIL(PMX_E_UNSUPPORTED, "pmx_pgm_split: not with backtracking");
+    if (c->pgm_long) FAIL(PMX_E_UNSUPPORTED, "pmx_pgm_split: prox_unity along the row dimension runs inside pmx_pgm_run only (a split iteration takes it as a user prox: host_prox)");
     const float* A = p.accelerated ? c->Xe[0] : c->X[0];
     const float* St = p.accelerated ? c->Xe[1] : c->X[1];
     const bool any_host = p.host_prox[0] || p.host_prox[1];
@@ -3526,6 +3602,7 @@ extern "C" int pmx_pgm_phase(pmx_ctx* c, int phase, int it) {
     if (!c->comm) FAIL(PMX_E_STATE, "pmx_set_comm_buffer has not been called");
     const pmx_pgm_params& p = c->pgm;
     if (p.bb_type || p.backtracking) FAIL(PMX_E_UNSUPPORTED, "row-sharded pgm supports the Lipschitz rule or fixed steps only");
+    if (c->pgm_long) FAIL(PMX_E_UNSUPPORTED, "row-sharded pgm does not contain prox_unity along the row dimension (its column sums span the ranks); pmx_pgm_run on one device does");
     if (c->ssplit && !c->comm_out) FAIL(PMX_E_STATE, "pmx_set_comm_out has not been called");
     const float* A = p.accelerated ? c->Xe[0] : c->X[0];
     const float* St = p.accelerated ? c->Xe[1] : c->X[1];

@@ -99,12 +99,13 @@ def prox_plus(X, step):
 
 
 def prox_unity(X, step, axis=0):
-    """Projection onto sum=1 along an axis (operators.py:41-45)."""
+    """Projection onto sum=1 along an axis (operators.py:41-45).  Along a factor's long axis (axis=0 on A, axis=1 on S) it
+    runs fused inside pgm / FISTA (one more launch per application); adaprox and bsdmm apply it between kernel launches."""
     return _apply(X, step, "unity", axis=axis)
 
 
 def prox_unity_plus(X, step, axis=0):
-    """Non-negative projection onto sum=1 along an axis (operators.py:48-52)."""
+    """Non-negative projection onto sum=1 along an axis (operators.py:48-52).  Long axis: see prox_unity."""
     return _apply(X, step, "unity_plus", axis=axis)
 
 
@@ -200,19 +201,27 @@ def _one_entry(prox, block):
 
 
 class NotFusable(NotImplementedError):
-    """An operator of this module that the fused solver kernels do not contain (prox_unity* along the long axis: a
-    grid-wide sum per application).  The solvers then apply it between kernel launches by calling it on the host copy of
-    its argument -- which runs the stand-alone device operator kernel -- one iteration per call."""
+    """An operator of this module that the solver asked about does not contain: prox_unity* along the long axis, a
+    grid-wide sum per application.  pgm / FISTA run it on the device (the update becomes a chain of launches, one more per
+    application: for_solver="pgm") unless the call has a line search, a user grad / step / prox or fp64 kernels; adaprox,
+    bsdmm and those pgm calls apply it between kernel launches by calling it on the host copy of its argument -- which
+    runs the stand-alone device operator kernel -- one iteration per call."""
+
+
+def has_long_axis(seq):
+    """Does a device operator sequence hold prox_unity* along the long axis of its block (pmx_prox.unit != 0)?"""
+    return any(seq.seq[i].unit != 0 for i in range(seq.n))
 
 
 def device_proxseq(prox, block, for_solver=False):
     """Translate a prox callable into a device operator sequence for factor `block` (0 = A, 1 = S).
     Returns a _lib.ProxSeq (n == 0 for prox=None) or raises NotImplementedError for callables that
-    are not (compositions of) this module's operators.  for_solver: also raise (NotFusable) for operators that exist
-    only as stand-alone kernels."""
+    are not (compositions of) this module's operators.  for_solver: also raise (NotFusable) for operators that the
+    solver's kernels do not contain -- True: adaprox, bsdmm and every host-driven route; "pgm": the fused pgm / FISTA
+    chain, which takes prox_unity* along the long axis."""
     if for_solver and prox is not None:
         seq = device_proxseq(prox, block)
-        if any(seq.seq[i].unit != 0 for i in range(seq.n)):
+        if for_solver != "pgm" and has_long_axis(seq):
             raise NotFusable("prox_unity along the long axis of block %d is applied between kernel launches" % block)
         return seq
     if prox is None:

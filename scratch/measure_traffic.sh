@@ -12,9 +12,10 @@ CFG=${1:-cfg3}; MODE=${2:-f16x2}; ROWS=${3:-}
 RFLAG=""; [ -n "$ROWS" ] && RFLAG="--rows $ROWS"
 for C in FETCH_SIZE WRITE_SIZE; do
   rm -rf $O/$C
-  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $O/$C -o p -- python bench.py --config $CFG --mode $MODE $RFLAG --steps 8 --warmup 2 --no-cpu > /dev/null 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $O/$C -o p -- python bench.py --config $CFG --mode $MODE $RFLAG --steps 8 --warmup 2 --no-cpu > $O/$C.log 2>&1 \
+    || { echo "$C pass failed (exit $?):"; tail -20 $O/$C.log; exit 1; }      # nothing more runs on the device after a failed pass
 done
-python - "$CFG" "$MODE" $O "$ROWS" <<'PY'
+python - "$CFG" "$MODE" $O "$ROWS" <<'PY' || exit 1
 import csv, glob, json, os, sys, time
 sys.path.insert(0, os.getcwd())
 import bench
