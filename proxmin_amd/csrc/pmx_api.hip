@@ -273,6 +273,16 @@ static bool prox_long_axis(const pmx_proxseq& p) {       // prox_unity* along th
         if ((p.seq[i].op == PMX_PROX_UNITY || p.seq[i].op == PMX_PROX_UNITY_PLUS) && p.seq[i].unit != 0) return true;
     return false;
 }
+// every operator is a coordinate-wise projection whose fixed point is reached in one pass (result independent of gamma)
+static bool seq_is_projection(const pmx_proxseq& p) {
+    for (int i = 0; i < p.n; ++i) {
+        const pmx_prox& q = p.seq[i];
+        const bool box = q.op == PMX_PROX_ID || q.op == PMX_PROX_ZERO || q.op == PMX_PROX_PLUS ||
+                         ((q.op == PMX_PROX_MIN || q.op == PMX_PROX_MAX || q.op == PMX_PROX_HARD || q.op == PMX_PROX_HARD_PLUS) && !q.relative);
+        if (!box) return false;
+    }
+    return true;
+}
 // long_axis_ok: the caller has a place for prox_unity* along the rows -- the stand-alone operator entry points (pmx_prox_apply /
 // pmx_prox_array) and pmx_pgm_begin (k_pgm_unity's chain)
 static int check_prox(const pmx_proxseq& p, const char* what, bool long_axis_ok = false) {
@@ -1447,6 +1457,35 @@ static int require_ready(pmx_ctx* c, bool f64_ok = false) {
     HIP_CHECK(hipSetDevice(c->device));
     return PMX_OK;
 }
+// The prologue of a solver entry point.  The caller may have changed the factors since the last call, so whatever the last update
+// kernel left behind for the next K1 / step rule is forgotten (reset_flags = false: pmx_adaprox_phase and pmx_adaprox_more_subs,
+// which carry absmax_by_finish from one phase call to the next); `algo`: the solver that must have been begun (ALG_NONE: any).
+static int begin_call(pmx_ctx* c, Algo algo, bool f64_ok, bool reset_flags = true) {
+    if (c && reset_flags) { c->absmax_by_finish = false; c->gram_by_update = false; }
+    int rc = require_ready(c, f64_ok);
+    if (rc != PMX_OK) return rc;
+    if (algo != ALG_NONE && c->algo != algo)
+        FAIL(PMX_E_STATE, "pmx_%s_begin has not been called", algo == ALG_PGM ? "pgm" : algo == ALG_ADAPROX ? "adaprox" : "bsdmm");
+    return PMX_OK;
+}
+// NesterovAccelerator.omega that the NEXT iteration will read (utils.py:198-206); advances the host's copy of t
+static double next_omega64(pmx_ctx* c) {
+    if (!c->pgm.accelerated) return 0.0;
+    const double t = c->nest_t;
+    const double t1 = 0.5 * (1.0 + sqrt(4.0 * t * t + 1.0));
+    c->nest_t = t1;
+    return (t - 1.0) / t1;
+}
+static float next_omega(pmx_ctx* c) { return (float)next_omega64(c); }
+// pgm's stopping test (algorithms.py:130-135) as a launch of its own; check = 0: a row-sharded iteration, whose sums are only this
+// rank's (the test is made after the next all-reduce, k_shard_post)
+static void enqueue_pgm_decide(pmx_ctx* c, int check = 1) {
+    DecideArgs d{};
+    d.status = c->dstatus; d.partials = c->partials;
+    d.e_rel[0] = c->pgm.e_rel[0]; d.e_rel[1] = c->pgm.e_rel[1];
+    d.check = check;
+    launch_pgm_decide(d, c->stream);
+}
 
 static void fill_result(pmx_ctx* c, pmx_result* r, int it_before) {
     if (!r) return;
@@ -1560,24 +1599,12 @@ static int pgm64_enqueue_iteration(pmx_ctx* c) {
     u.status = c->dstatus;
     u.partials = c->partials;
     u.accelerated = p.accelerated;
-    {   // omega the NEXT iteration reads (utils.py:198-206), in fp64
-        double om = 0.0;
-        if (p.accelerated) {
-            const double t = c->nest_t, t1 = 0.5 * (1.0 + sqrt(4.0 * t * t + 1.0));
-            om = (t - 1.0) / t1;
-            c->nest_t = t1;
-        }
-        u.omega_next = om;
-    }
+    u.omega_next = next_omega64(c);
     const int64_t rmax = c->rows[0] > c->rows[1] ? c->rows[0] : c->rows[1];
     const int nbx = (int)((rmax + EW_THREADS / 32 - 1) / (EW_THREADS / 32));      // <= 256: M, N <= 8192
     if (c->f64big) launch_pgm64b_update(u, c->stream);
     else launch_pgm64_update(u, nbx, c->stream);                                   // algorithms.py:107-108
-    DecideArgs d{};
-    d.status = c->dstatus; d.partials = c->partials;
-    d.e_rel[0] = p.e_rel[0]; d.e_rel[1] = p.e_rel[1];
-    d.check = 1;
-    launch_pgm_decide(d, c->stream);                                               // algorithms.py:130-135
+    enqueue_pgm_decide(c);                                                         // algorithms.py:130-135
     HIP_CHECK(hipGetLastError());
     c->it += 1;
     return PMX_OK;
@@ -1656,20 +1683,10 @@ static int pgm64_bt_iteration(pmx_ctx* c) {
     }
     c->bt_fprev = f_now;                                         // :127
     // the stopping test (:130-135) from the sums of the accepted trial: k_pgm_decide folds the same slots
-    DecideArgs d{};
-    d.status = c->dstatus; d.partials = c->partials;
-    d.e_rel[0] = p.e_rel[0]; d.e_rel[1] = p.e_rel[1];
-    d.check = 1;
-    launch_pgm_decide(d, c->stream);
+    enqueue_pgm_decide(c);
     BtFin64Args fin{};
-    double om = 0.0;
-    if (p.accelerated) {                                         // omega the NEXT iteration reads (utils.py:198-206)
-        const double t = c->nest_t, t1 = 0.5 * (1.0 + sqrt(4.0 * t * t + 1.0));
-        om = (t - 1.0) / t1;
-        c->nest_t = t1;
-    }
     for (int j = 0; j < 2; ++j) { fin.X[j] = c->Xd[j]; fin.Xp[j] = c->Xprevd[j]; fin.E[j] = c->Xed[j]; fin.count[j] = c->rows[j] * c->K; }
-    fin.omega = om;
+    fin.omega = next_omega64(c);
     fin.status = c->dstatus;
     launch_bt64_finish(fin, c->stream);
     HIP_CHECK(hipGetLastError());
@@ -1813,6 +1830,56 @@ static float* s_view(pmx_ctx* c, int j, float* p) { return (p && j == 1 && c->ss
 static int64_t upd_rows(pmx_ctx* c, int j) { return (j == 1 && c->ssplit) ? c->sncol : c->rows[j]; }
 static int64_t split_chunk(pmx_ctx* c) { return c->sncol * c->K + (int64_t)c->KP * c->KP + 2 * MAXK + 32; }
 
+// ONE slab of K floats per row at `base` in place of K1's: a gradient that is folded already (the G buffer), or the reduced gS of a
+// row-sharded iteration.  No kernel reads `stride` when n == 1, and the routes differ in what they leave there (see the call sites).
+static SlabRef single_slab(const float* base, int64_t K, int64_t stride = 0) {
+    SlabRef s;
+    s.base = base; s.n = 1; s.stride = stride; s.ld = (int)K;
+    return s;
+}
+// row-sharded: gSt is the all-reduced sum sitting in the comm buffer (S-split: this rank's chunk of it, after the reduce-scatter);
+// stride as slab_ref(c, 1) leaves it
+static SlabRef comm_slab(pmx_ctx* c) { return single_slab(c->ssplit ? c->comm_out : c->comm, c->K, c->rowsK[1] * c->Kk); }
+
+// What every route to k_pgm_update passes: the fused run adds the ticket, grid, maxima and Gram outputs, the split iteration its
+// mode / T / stepArr and the folded G as the slab, the row-sharded one the comm slab.  omega_next is the caller's: next_omega()
+// advances the Nesterov sequence, once per iteration.  own_S: S-split, block 1 is this rank's sncol columns of S (rows of S^T) only.
+static PgmArgs pgm_args(pmx_ctx* c, bool own_S = false) {
+    const pmx_pgm_params& p = c->pgm;
+    PgmArgs u{};
+    for (int j = 0; j < 2; ++j) {
+        float* Xe = p.accelerated ? c->Xe[j] : c->X[j];
+        u.X[j] = own_S ? s_view(c, j, c->X[j]) : c->X[j];
+        u.Xe[j] = own_S ? s_view(c, j, Xe) : Xe;
+        u.G[j] = own_S ? s_view(c, j, c->G[j]) : c->G[j];
+        u.slab[j] = slab_ref(c, j);
+        u.rows[j] = own_S ? upd_rows(c, j) : c->rows[j];
+        u.prox[j] = to_dev(p.prox[j]);
+    }
+    u.K = (int)c->K;
+    u.status = c->dstatus;
+    u.partials = c->partials;
+    u.accelerated = p.accelerated;
+    return u;
+}
+// the Barzilai-Borwein rule on the device (step(*_X, it, grads=G): utils.py:216-241) at the point A, St; k_bb_reduce folds the gradient as well
+static void enqueue_bb(pmx_ctx* c, const float* A, const float* St) {
+    const pmx_pgm_params& p = c->pgm;
+    BBArgs b{};
+    b.X[0] = A; b.X[1] = St;
+    for (int j = 0; j < 2; ++j) {
+        b.slab[j] = slab_ref(c, j);
+        b.G[j] = c->G[j]; b.Xprev[j] = c->bbX[j]; b.Gprev[j] = c->bbG[j];
+        b.rows[j] = c->rows[j];
+    }
+    b.K = (int)c->K; b.status = c->dstatus; b.partials = c->partials;
+    b.first = c->it == 0;
+    launch_bb_reduce(b, c->stream);
+    BBStepArgs bs{};
+    bs.status = c->dstatus; bs.partials = c->partials; bs.it = c->it; bs.type = p.bb_type; bs.init_r = p.bb_init_r;
+    launch_bb_step(bs, c->stream);
+}
+
 static AlphaArgs alpha_args(pmx_ctx* c) {
     AlphaArgs a{};
     a.status = c->dstatus;
@@ -1942,8 +2009,8 @@ extern "C" int pmx_bb_sums(int device, int is_f64, const void* X, const void* Xp
 // PGM / FISTA                                             (proxmin/algorithms.py:12-144)
 // ------------------------------------------------------------------------------------------------
 extern "C" int pmx_pgm_begin(pmx_ctx* c, const pmx_pgm_params* p) {
-    if (c) { c->absmax_by_finish = false; c->gram_by_update = false; c->bt_grad_fresh = false; }
-    int rc = require_ready(c, true);
+    if (c) c->bt_grad_fresh = false;
+    int rc = begin_call(c, ALG_NONE, true);
     if (rc != PMX_OK) return rc;
     if (!p) FAIL(PMX_E_INVALID, "params is NULL");
     bool long_axis = false;
@@ -2051,16 +2118,6 @@ extern "C" int pmx_pgm_begin(pmx_ctx* c, const pmx_pgm_params* p) {
     return PMX_OK;
 }
 
-// omega that the NEXT iteration will read (utils.py:198-206)
-static float next_omega(pmx_ctx* c) {
-    if (!c->pgm.accelerated) return 0.f;
-    const double t = c->nest_t;
-    const double t1 = 0.5 * (1.0 + sqrt(4.0 * t * t + 1.0));
-    const double om = (t - 1.0) / t1;
-    c->nest_t = t1;
-    return (float)om;
-}
-
 // The update of a context whose operator sequences hold prox_unity* along the rows (pmx_ctx::pgm_long): the sequence of block j,
 // unrolled over `repeat`, is cut at its L_j such entries; max(L_A, L_S) + 1 launches of k_pgm_unity (k_update.hip) -- head, middles,
 // finish.  A block with fewer applications idles between its last sum and the finish launch; one without any is updated whole there.
@@ -2143,35 +2200,10 @@ static int pgm_enqueue_iteration(pmx_ctx* c) {
             if (rc != PMX_OK) return rc;
         }
     }
-    if (p.bb_type) {                                                      // step(*_X, it, grads=G): utils.py:216-241
-        BBArgs b{};
-        b.X[0] = A; b.X[1] = St;
-        for (int j = 0; j < 2; ++j) {
-            b.slab[j] = slab_ref(c, j);
-            b.G[j] = c->G[j]; b.Xprev[j] = c->bbX[j]; b.Gprev[j] = c->bbG[j];
-            b.rows[j] = c->rows[j];
-        }
-        b.K = (int)c->K; b.status = c->dstatus; b.partials = c->partials;
-        b.first = c->it == 0;
-        launch_bb_reduce(b, c->stream);
-        BBStepArgs bs{};
-        bs.status = c->dstatus; bs.partials = c->partials; bs.it = c->it; bs.type = p.bb_type; bs.init_r = p.bb_init_r;
-        launch_bb_step(bs, c->stream);
-    }
-    PgmArgs u{};
-    for (int j = 0; j < 2; ++j) {
-        u.X[j] = c->X[j];
-        u.Xe[j] = p.accelerated ? c->Xe[j] : c->X[j];
-        u.G[j] = c->G[j];
-        u.slab[j] = slab_ref(c, j);
-        if (p.bb_type) { u.slab[j].base = c->G[j]; u.slab[j].n = 1; u.slab[j].ld = (int)c->K; u.slab[j].extra = nullptr; }    // already folded by k_bb_reduce
-        u.rows[j] = c->rows[j];
-        u.prox[j] = to_dev(p.prox[j]);
-    }
-    u.K = (int)c->K;
-    u.status = c->dstatus;
-    u.partials = c->partials;
-    u.accelerated = p.accelerated;
+    if (p.bb_type) enqueue_bb(c, A, St);
+    PgmArgs u = pgm_args(c);
+    if (p.bb_type)      // already folded by k_bb_reduce (this route keeps K1's slab stride in the unread field; a split iteration leaves 0 there)
+        for (int j = 0; j < 2; ++j) u.slab[j] = single_slab(c->G[j], c->K, u.slab[j].stride);
     u.omega_next = next_omega(c);
     // the stopping test (algorithms.py:130-135) is made by the last of the update kernel's 2 x EW_BLOCKS workgroups
     if (c->ticketLaunches >= (1u << 30)) {
@@ -2321,11 +2353,7 @@ static int bt_step(pmx_ctx* c, int phase, int* need, double eff[2]) {
     fin.K = (int)c->K; fin.status = c->dstatus;
     fin.omega_next = next_omega(c);
     launch_bt_finish(fin, c->stream);
-    DecideArgs d{};
-    d.status = c->dstatus; d.partials = c->partials;
-    d.e_rel[0] = p.e_rel[0]; d.e_rel[1] = p.e_rel[1];
-    d.check = 1;
-    launch_pgm_decide(d, c->stream);
+    enqueue_pgm_decide(c);
     HIP_CHECK(hipGetLastError());
     c->it += 1;
     return PMX_OK;
@@ -2345,11 +2373,7 @@ static int set_fixed_steps(pmx_ctx* c, const double s[2]) {
 
 static int pgm_flush_decide(pmx_ctx* c) {
     if (!c->decide_pending) return PMX_OK;
-    DecideArgs d{};
-    d.status = c->dstatus; d.partials = c->partials;
-    d.e_rel[0] = c->pgm.e_rel[0]; d.e_rel[1] = c->pgm.e_rel[1];
-    d.check = 1;
-    launch_pgm_decide(d, c->stream);
+    enqueue_pgm_decide(c);
     HIP_CHECK(hipGetLastError());
     c->decide_pending = false;
     return PMX_OK;
@@ -2439,8 +2463,7 @@ extern "C" int pmx_pgm_step_arrays(pmx_ctx* c, int mask) {
 }
 
 extern "C" int pmx_pgm_bt_split(pmx_ctx* c, int phase, int* need, double eff_steps[2], pmx_result* res) {
-    if (c) { c->absmax_by_finish = false; c->gram_by_update = false; }
-    int rc = require_ready(c);
+    int rc = begin_call(c, ALG_NONE, false);       // (the solver is checked below, together with its line search)
     if (rc != PMX_OK) return rc;
     if (!need || !eff_steps) FAIL(PMX_E_INVALID, "NULL argument");
     if (c->algo != ALG_PGM || !c->pgm.backtracking) FAIL(PMX_E_STATE, "pmx_pgm_begin has not been called with backtracking");
@@ -2463,10 +2486,8 @@ extern "C" int pmx_pgm_bt_split(pmx_ctx* c, int phase, int* need, double eff_ste
 }
 
 extern "C" int pmx_pgm_split(pmx_ctx* c, int phase, const double* steps, pmx_result* res) {
-    if (c) { c->absmax_by_finish = false; c->gram_by_update = false; }
-    int rc = require_ready(c);
+    int rc = begin_call(c, ALG_PGM, false);
     if (rc != PMX_OK) return rc;
-    if (c->algo != ALG_PGM) FAIL(PMX_E_STATE, "pmx_pgm_begin has not been called");
     const pmx_pgm_params& p = c->pgm;
     // (phase 0 alone -- the gradient at the evaluation point, for a user `step` that wants `grads` -- is harmless next to
     //  the line search: the iteration itself then runs through pmx_pgm_run(ctx, 1) with the steps of pmx_pgm_set_fixed_steps)
@@ -2476,24 +2497,14 @@ extern "C" int pmx_pgm_split(pmx_ctx* c, int phase, const double* steps, pmx_res
     const float* St = p.accelerated ? c->Xe[1] : c->X[1];
     const bool any_host = p.host_prox[0] || p.host_prox[1];
     auto update = [&](int stage) {       // stage 1: "pre" of the host blocks; stage 2: the update
-        PgmArgs u{};
+        PgmArgs u = pgm_args(c);
         for (int j = 0; j < 2; ++j) {
-            u.X[j] = c->X[j];
-            u.Xe[j] = p.accelerated ? c->Xe[j] : c->X[j];
-            u.G[j] = c->G[j];
-            u.slab[j].base = c->G[j];    // folded by phase 0
-            u.slab[j].n = 1; u.slab[j].ld = (int)c->K;
-            u.rows[j] = c->rows[j];
-            u.prox[j] = to_dev(p.prox[j]);
+            u.slab[j] = single_slab(c->G[j], c->K);    // folded by phase 0
             u.T[j] = c->Xp[j];
             u.stepArr[j] = (c->step_arr_mask >> j) & 1 ? c->stepArr[j] : nullptr;
             u.mode[j] = stage == 1 ? (p.host_prox[j] ? 1 : 3) : (p.host_prox[j] ? 2 : 0);
         }
-        u.K = (int)c->K;
-        u.status = c->dstatus;
-        u.partials = c->partials;
-        u.accelerated = p.accelerated;
-        u.omega_next = stage == 2 ? next_omega(c) : 0.f;
+        u.omega_next = stage == 2 ? next_omega(c) : 0.f;       // (stage 1 does not advance the Nesterov sequence)
         launch_pgm_update(u, c->stream);
     };
     switch (phase) {
@@ -2511,20 +2522,8 @@ extern "C" int pmx_pgm_split(pmx_ctx* c, int phase, const double* steps, pmx_res
             rc = enqueue_grad(c, A, St, 1, 1);
             if (rc != PMX_OK) return rc;
             c->bt_grad_fresh = p.backtracking != 0;      // (the line search's phase 0 evaluates the same point: Xe)
-            if (p.bb_type) {             // the Barzilai-Borwein rule on the device (utils.py:216-241), exactly as a fused iteration
-                BBArgs b{};              // does it: k_bb_reduce folds the gradient as well
-                b.X[0] = A; b.X[1] = St;
-                for (int j = 0; j < 2; ++j) {
-                    b.slab[j] = slab_ref(c, j);
-                    b.G[j] = c->G[j]; b.Xprev[j] = c->bbX[j]; b.Gprev[j] = c->bbG[j];
-                    b.rows[j] = c->rows[j];
-                }
-                b.K = (int)c->K; b.status = c->dstatus; b.partials = c->partials;
-                b.first = c->it == 0;
-                launch_bb_reduce(b, c->stream);
-                BBStepArgs bs{};
-                bs.status = c->dstatus; bs.partials = c->partials; bs.it = c->it; bs.type = p.bb_type; bs.init_r = p.bb_init_r;
-                launch_bb_step(bs, c->stream);
+            if (p.bb_type) {             // exactly as a fused iteration does it
+                enqueue_bb(c, A, St);
             } else {
                 FoldArgs f{};
                 for (int j = 0; j < 2; ++j) { f.slab[j] = slab_ref(c, j); f.G[j] = c->G[j]; f.rows[j] = c->rows[j]; }
@@ -2549,12 +2548,7 @@ extern "C" int pmx_pgm_split(pmx_ctx* c, int phase, const double* steps, pmx_res
             const int it0 = c->hstatus->it_done;
             if (steps) { rc = set_fixed_steps(c, steps); if (rc != PMX_OK) return rc; }
             update(2);
-            DecideArgs d{};
-            d.status = c->dstatus;
-            d.partials = c->partials;
-            d.e_rel[0] = p.e_rel[0]; d.e_rel[1] = p.e_rel[1];
-            d.check = 1;
-            launch_pgm_decide(d, c->stream);
+            enqueue_pgm_decide(c);
             HIP_CHECK(hipGetLastError());
             c->it += 1;
             rc = read_status(c);
@@ -2570,8 +2564,7 @@ extern "C" int pmx_pgm_split(pmx_ctx* c, int phase, const double* steps, pmx_res
 // adaprox                                                 (proxmin/algorithms.py:248-423)
 // ------------------------------------------------------------------------------------------------
 extern "C" int pmx_adaprox_begin(pmx_ctx* c, const pmx_adaprox_params* p, int warm_moments) {
-    if (c) { c->absmax_by_finish = false; c->gram_by_update = false; }
-    int rc = require_ready(c, true);
+    int rc = begin_call(c, ALG_NONE, true);
     if (rc != PMX_OK) return rc;
     if (!p) FAIL(PMX_E_INVALID, "params is NULL");
     if (p->scheme < PMX_ADAM || p->scheme > PMX_RADAM) FAIL(PMX_E_INVALID, "unknown scheme %d", p->scheme);
@@ -2731,22 +2724,22 @@ static int ada_enqueue_tail(pmx_ctx* c, int t) {
     return PMX_OK;
 }
 
-static int ada_enqueue_moment(pmx_ctx* c, int it, double b1t, double b1prev) {
+// The moment + update phase of iteration `it` (algorithms.py:375-378), for k_ada_moment (the chain) and for k_ada_tail (for_tail).
+// The two differ on purpose: the chain keeps Psi in memory for k_ada_sub -- and for a host-side proximal loop, which therefore
+// counts in has_prox --; the fused tail holds Psi in LDS (nullptr here) and exists with device operators only.
+static MomentArgs moment_args(pmx_ctx* c, int it, double b1t, double b1prev, bool for_tail) {
     const pmx_adaprox_params& p = c->ada;
     MomentArgs m{};
     for (int j = 0; j < 2; ++j) {
         m.X[j] = s_view(c, j, c->X[j]); m.Xp[j] = s_view(c, j, c->Xp[j]);
         m.Mm[j] = s_view(c, j, c->Mm[j]); m.Vv[j] = s_view(c, j, c->Vv[j]);
         m.Vh[j] = p.warm_vhat ? s_view(c, j, c->Vh[j]) : nullptr;
-        m.Psi[j] = s_view(c, j, c->Psi[j]);
+        m.Psi[j] = for_tail ? nullptr : s_view(c, j, c->Psi[j]);
         m.slab[j] = slab_ref(c, j);
         m.rows[j] = upd_rows(c, j);
-        m.has_prox[j] = p.prox[j].n > 0 || p.host_prox[j];   // (Psi is kept for a host-side proximal loop as well)
+        m.has_prox[j] = p.prox[j].n > 0 || (!for_tail && p.host_prox[j]);
     }
-    if (c->shard_grad_from_comm) {   // row-sharded: gSt is the all-reduced sum sitting in the comm buffer (S-split: this rank's chunk of it)
-        m.slab[1].base = c->ssplit ? c->comm_out : c->comm;
-        m.slab[1].n = 1; m.slab[1].ld = (int)c->K; m.slab[1].extra = nullptr;
-    }
+    if (c->shard_grad_from_comm) m.slab[1] = comm_slab(c);
     m.K = (int)c->K;
     m.status = c->dstatus;
     m.partials = c->partials;
@@ -2754,7 +2747,10 @@ static int ada_enqueue_moment(pmx_ctx* c, int it, double b1t, double b1prev) {
     m.it = it;
     m.b1t = b1t; m.b1prev = b1prev; m.b2 = p.b2; m.eps = p.eps; m.p = p.p;
     m.check_convergence = p.check_convergence;
-    launch_ada_moment(m, c->stream);                                      // algorithms.py:375-378
+    return m;
+}
+static int ada_enqueue_moment(pmx_ctx* c, int it, double b1t, double b1prev) {
+    launch_ada_moment(moment_args(c, it, b1t, b1prev, false), c->stream);
     HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }
@@ -2763,27 +2759,12 @@ static int ada_enqueue_moment(pmx_ctx* c, int it, double b1t, double b1prev) {
 static int ada_enqueue_tail_fused(pmx_ctx* c, int it, double b1t, double b1prev) {
     const pmx_adaprox_params& p = c->ada;
     TailArgs t{};
-    MomentArgs& m = t.m;
+    t.m = moment_args(c, it, b1t, b1prev, true);
     for (int j = 0; j < 2; ++j) {
-        m.X[j] = s_view(c, j, c->X[j]); m.Xp[j] = s_view(c, j, c->Xp[j]);
-        m.Mm[j] = s_view(c, j, c->Mm[j]); m.Vv[j] = s_view(c, j, c->Vv[j]);
-        m.Vh[j] = p.warm_vhat ? s_view(c, j, c->Vh[j]) : nullptr;
-        m.Psi[j] = nullptr;
-        m.slab[j] = slab_ref(c, j);
-        m.rows[j] = upd_rows(c, j);
-        m.has_prox[j] = p.prox[j].n > 0;
         t.prox[j] = to_dev(p.prox[j]);
         t.e_rel[j] = p.e_rel[j];
         t.slots[j] = (int)((upd_rows(c, j) + 8191) / 8192);
     }
-    if (c->shard_grad_from_comm) { m.slab[1].base = c->ssplit ? c->comm_out : c->comm; m.slab[1].n = 1; m.slab[1].ld = (int)c->K; m.slab[1].extra = nullptr; }
-    m.K = (int)c->K;
-    m.status = c->dstatus;
-    m.partials = c->partials;
-    m.scheme = p.scheme;
-    m.it = it;
-    m.b1t = b1t; m.b1prev = b1prev; m.b2 = p.b2; m.eps = p.eps; m.p = p.p;
-    m.check_convergence = p.check_convergence;
     t.prox_max_iter = p.prox_max_iter;
     t.colpart = c->colpart;
     t.absmax_out = k1_fp16(c->k1) ? c->absmax : nullptr;
@@ -2824,11 +2805,57 @@ static int ada_enqueue_head(pmx_ctx* c, int it, double b1t, double b1prev, bool 
     return ada_enqueue_moment(c, it, b1t, b1prev);
 }
 
-extern "C" int pmx_adaprox_run(pmx_ctx* c, int n_iter, const double* b1, double b1_prev, pmx_result* res) {
-    if (c) { c->absmax_by_finish = false; c->gram_by_update = false; }
-    int rc = require_ready(c, true);
+// proximal passes to enqueue with an iteration (`wanted`: the loops' recent length, capped by prox_max_iter; none without a device
+// operator), and passes per launch for them: 4 when the loops have been ending within 4 passes (the usual steady state: 1 pass for a
+// projection, 2-3 for prox_unity_plus), else 8; PMX_SUB_BATCH=1 keeps one pass per launch
+static int ada_pick_sub_batch(pmx_ctx* c, int wanted) {
+    const pmx_adaprox_params& p = c->ada;
+    const bool any_prox = p.prox[0].n > 0 || p.prox[1].n > 0;
+    const int nsub = any_prox ? std::max(1, std::min(wanted, p.prox_max_iter)) : 0;
+    if (c->sub_nt != 1) c->sub_nt = nsub <= 4 ? 4 : SUB_NT_MAX;
+    return nsub;
+}
+// A chain stopped inside an iteration's proximal loop (HALT_NEED_SUB) with *t_enq passes enqueued: feed it more, and its tail again.
+// The caller reads the status afterwards.
+static int ada_feed_more_subs(pmx_ctx* c, int* t_enq) {
+    int rc = clear_halt(c);
     if (rc != PMX_OK) return rc;
-    if (c->algo != ALG_ADAPROX) FAIL(PMX_E_STATE, "pmx_adaprox_begin has not been called");
+    *t_enq = ada_enqueue_subs(c, *t_enq, std::min(std::max(4, *t_enq), 64));
+    return ada_enqueue_tail(c, *t_enq);
+}
+
+// one fp64 adaprox iteration's arguments (k64_ada_iter; k_big_f64.hip's chain wraps them in Ada64bArgs)
+static Ada64Args ada64_args(pmx_ctx* c, int it, double b1t, double b1prev) {
+    const pmx_adaprox_params& p = c->ada;
+    Ada64Args a{};
+    for (int j = 0; j < 2; ++j) {
+        a.X[j] = c->Xd[j]; a.Xp[j] = c->Xpd[j]; a.Mm[j] = c->Md[j]; a.Vv[j] = c->Vd[j];
+        a.Vh[j] = p.warm_vhat ? c->Vhd[j] : nullptr;
+        a.Psi[j] = c->Psid[j]; a.z[j] = c->zd[j];
+        a.slab[j] = c->slabd[j];
+        a.nslab[j] = j == 0 ? c->nSlabA : c->nSlabS;
+        a.rows[j] = c->rows[j];
+        a.prox[j] = to_dev(p.prox[j]);
+        a.has_prox[j] = p.prox[j].n > 0;
+        a.e_rel[j] = p.e_rel[j];
+        a.fixed[j] = p.fixed_alpha[j];
+    }
+    a.K = (int)c->K;
+    a.status = c->dstatus;
+    a.scheme = p.scheme;
+    a.it = it;
+    a.b1t = b1t; a.b1prev = b1prev;
+    a.b2 = p.b2; a.eps = p.eps; a.p = p.p;
+    a.check_convergence = p.check_convergence;
+    a.prox_max_iter = p.prox_max_iter;
+    a.use_fixed = p.use_fixed_steps;
+    a.alpha_out = c->alpha64;
+    return a;
+}
+
+extern "C" int pmx_adaprox_run(pmx_ctx* c, int n_iter, const double* b1, double b1_prev, pmx_result* res) {
+    int rc = begin_call(c, ALG_ADAPROX, true);
+    if (rc != PMX_OK) return rc;
     if (n_iter < 0 || (n_iter > 0 && !b1)) FAIL(PMX_E_INVALID, "bad n_iter / b1");
     for (int i = 0; i < n_iter; ++i)
         if (!(b1[i] >= 0 && b1[i] < 1)) FAIL(PMX_E_INVALID, "b1 out of [0,1)");       // algorithms.py:330
@@ -2838,29 +2865,7 @@ extern "C" int pmx_adaprox_run(pmx_ctx* c, int n_iter, const double* b1, double 
     if (c->f64big) {         // [r6] k_big_f64.hip: two MFMA passes, then the tail as a chain of launches; the proximal loops' lengths are guessed
         auto args_of = [&](int gi) {
             Ada64bArgs b{};
-            Ada64Args& a = b.a;
-            for (int j = 0; j < 2; ++j) {
-                a.X[j] = c->Xd[j]; a.Xp[j] = c->Xpd[j]; a.Mm[j] = c->Md[j]; a.Vv[j] = c->Vd[j];
-                a.Vh[j] = p.warm_vhat ? c->Vhd[j] : nullptr;
-                a.Psi[j] = c->Psid[j]; a.z[j] = c->zd[j];
-                a.slab[j] = c->slabd[j];
-                a.nslab[j] = j == 0 ? c->nSlabA : c->nSlabS;
-                a.rows[j] = c->rows[j];
-                a.prox[j] = to_dev(p.prox[j]);
-                a.has_prox[j] = p.prox[j].n > 0;
-                a.e_rel[j] = p.e_rel[j];
-                a.fixed[j] = p.fixed_alpha[j];
-            }
-            a.K = (int)c->K;
-            a.status = c->dstatus;
-            a.scheme = p.scheme;
-            a.it = it0 + gi;
-            a.b1t = b1[gi]; a.b1prev = gi == 0 ? b1_prev : b1[gi - 1];
-            a.b2 = p.b2; a.eps = p.eps; a.p = p.p;
-            a.check_convergence = p.check_convergence;
-            a.prox_max_iter = p.prox_max_iter;
-            a.use_fixed = p.use_fixed_steps;
-            a.alpha_out = c->alpha64;
+            b.a = ada64_args(c, it0 + gi, b1[gi], gi == 0 ? b1_prev : b1[gi - 1]);
             b.partials = c->partials;
             b.colpart = c->colpart64;
             return b;
@@ -2910,30 +2915,7 @@ extern "C" int pmx_adaprox_run(pmx_ctx* c, int n_iter, const double* b1, double 
             for (int i = 0; i < std::min(left, 16); ++i, ++gi) {
                 rc = enqueue_front64(c, c->Xd[0], c->Xd[1], 1, 1, true, false, 1.0);       // algorithms.py:369
                 if (rc != PMX_OK) return rc;
-                Ada64Args a{};
-                for (int j = 0; j < 2; ++j) {
-                    a.X[j] = c->Xd[j]; a.Xp[j] = c->Xpd[j]; a.Mm[j] = c->Md[j]; a.Vv[j] = c->Vd[j];
-                    a.Vh[j] = p.warm_vhat ? c->Vhd[j] : nullptr;
-                    a.Psi[j] = c->Psid[j]; a.z[j] = c->zd[j];
-                    a.slab[j] = c->slabd[j];
-                    a.nslab[j] = j == 0 ? c->nSlabA : c->nSlabS;
-                    a.rows[j] = c->rows[j];
-                    a.prox[j] = to_dev(p.prox[j]);
-                    a.has_prox[j] = p.prox[j].n > 0;
-                    a.e_rel[j] = p.e_rel[j];
-                    a.fixed[j] = p.fixed_alpha[j];
-                }
-                a.K = (int)c->K;
-                a.status = c->dstatus;
-                a.scheme = p.scheme;
-                a.it = it0 + gi;
-                a.b1t = b1[gi]; a.b1prev = gi == 0 ? b1_prev : b1[gi - 1];
-                a.b2 = p.b2; a.eps = p.eps; a.p = p.p;
-                a.check_convergence = p.check_convergence;
-                a.prox_max_iter = p.prox_max_iter;
-                a.use_fixed = p.use_fixed_steps;
-                a.alpha_out = c->alpha64;
-                launch_ada64_iter(a, c->stream);                                           // algorithms.py:370-410
+                launch_ada64_iter(ada64_args(c, it0 + gi, b1[gi], gi == 0 ? b1_prev : b1[gi - 1]), c->stream);   // algorithms.py:370-410
                 HIP_CHECK(hipGetLastError());
             }
             rc = read_status(c);
@@ -2949,10 +2931,7 @@ extern "C" int pmx_adaprox_run(pmx_ctx* c, int n_iter, const double* b1, double 
         // ---- enqueue a chunk of whole iterations ------------------------------------------------
         // (the fused tail decides its proximal loops on the device: nothing to speculate on, longer chunks between host syncs)
         const int chunk = std::min(n_iter - done, c->tail_fused ? 64 : 16);
-        const int nsub = any_prox ? std::max(1, std::min(c->nsub_guess, p.prox_max_iter)) : 0;
-        // passes per launch for this chunk: 4 when the loops have been ending within 4 passes (the usual steady state:
-        // 1 pass for a projection, 2-3 for prox_unity_plus), else 8; PMX_SUB_BATCH=1 keeps one pass per launch
-        if (c->sub_nt != 1) c->sub_nt = nsub <= 4 ? 4 : SUB_NT_MAX;
+        const int nsub = ada_pick_sub_batch(c, c->nsub_guess);       // (passes per launch: fixed for this chunk)
         for (int i = 0; i < chunk; ++i) {
             const int gi = done + i;
             if (c->tail_fused) {
@@ -2974,11 +2953,7 @@ extern "C" int pmx_adaprox_run(pmx_ctx* c, int n_iter, const double* b1, double 
         const int nsub_enq = nsub > 0 ? ((nsub + c->sub_nt - 1) / c->sub_nt) * c->sub_nt : 0;
         int t_enq = nsub_enq;
         while (c->hstatus->halt && c->hstatus->reason == HALT_NEED_SUB) {
-            rc = clear_halt(c);
-            if (rc != PMX_OK) return rc;
-            const int more = std::min(std::max(4, t_enq), 64);
-            t_enq = ada_enqueue_subs(c, t_enq, more);
-            rc = ada_enqueue_tail(c, t_enq);
+            rc = ada_feed_more_subs(c, &t_enq);
             if (rc != PMX_OK) return rc;
             // the iterations that followed in the chunk were skipped: re-enqueue them after this one
             const int finished_if_ok = c->hstatus->it_done - it0 + 1;
@@ -3030,10 +3005,8 @@ extern "C" int pmx_adaprox_set_alpha(pmx_ctx* c, const float* alpha) {
 }
 
 extern "C" int pmx_adaprox_split(pmx_ctx* c, int phase, int it, double b1_it, double b1_prev, const int* host_tau, double* maxpsi, pmx_result* res) {
-    if (c) { c->absmax_by_finish = false; c->gram_by_update = false; }
-    int rc = require_ready(c);
+    int rc = begin_call(c, ALG_ADAPROX, false);
     if (rc != PMX_OK) return rc;
-    if (c->algo != ALG_ADAPROX) FAIL(PMX_E_STATE, "pmx_adaprox_begin has not been called");
     if (c->tail_fused) FAIL(PMX_E_STATE, "pmx_adaprox_split needs a context begun with host_prox");
     if (!(b1_it >= 0 && b1_it < 1)) FAIL(PMX_E_INVALID, "b1 out of [0,1)");
     const pmx_adaprox_params& p = c->ada;
@@ -3059,18 +3032,13 @@ extern "C" int pmx_adaprox_split(pmx_ctx* c, int phase, int it, double b1_it, do
     c->host_tau[1] = host_tau ? host_tau[1] : 0;
     const bool any_prox = p.prox[0].n > 0 || p.prox[1].n > 0;
     const int it0 = c->hstatus->it_done;
-    const int nsub = any_prox ? std::max(1, std::min(c->nsub_guess, p.prox_max_iter)) : 0;
-    if (c->sub_nt != 1) c->sub_nt = nsub <= 4 ? 4 : SUB_NT_MAX;
-    int t_enq = ada_enqueue_subs(c, 0, nsub);
+    int t_enq = ada_enqueue_subs(c, 0, ada_pick_sub_batch(c, c->nsub_guess));
     rc = ada_enqueue_tail(c, t_enq);
     if (rc != PMX_OK) return rc;
     rc = read_status(c);
     if (rc != PMX_OK) return rc;
     while (c->hstatus->halt && c->hstatus->reason == HALT_NEED_SUB) {
-        rc = clear_halt(c);
-        if (rc != PMX_OK) return rc;
-        t_enq = ada_enqueue_subs(c, t_enq, std::min(std::max(4, t_enq), 64));
-        rc = ada_enqueue_tail(c, t_enq);
+        rc = ada_feed_more_subs(c, &t_enq);
         if (rc != PMX_OK) return rc;
         rc = read_status(c);
         if (rc != PMX_OK) return rc;
@@ -3086,8 +3054,7 @@ extern "C" int pmx_adaprox_split(pmx_ctx* c, int phase, int it, double b1_it, do
 // block-SDMM                                              (proxmin/algorithms.py:653-850)
 // ------------------------------------------------------------------------------------------------
 extern "C" int pmx_bsdmm_begin(pmx_ctx* c, const pmx_bsdmm_params* p) {
-    if (c) { c->absmax_by_finish = false; c->gram_by_update = false; }
-    int rc = require_ready(c, true);
+    int rc = begin_call(c, ALG_NONE, true);
     if (rc != PMX_OK) return rc;
     if (!p) FAIL(PMX_E_INVALID, "params is NULL");
     if (c->W || c->Wd_on)                              // bsdmm's steps come from nmf.step_pgm (nmf.py:187-193)
@@ -3138,6 +3105,57 @@ extern "C" int pmx_bsdmm_begin(pmx_ctx* c, const pmx_bsdmm_params* p) {
     return PMX_OK;
 }
 
+// What every route to k_bsdmm_update passes for block j.  The fused run adds the Gram and maxima outputs, the split iteration its
+// stage / host_f / host_g and the T / Tf buffers, the row-sharded one the comm slab; each is zero wherever it is not named.
+static BsdmmArgs bsdmm_args(pmx_ctx* c, int j) {
+    const pmx_bsdmm_params& p = c->bsd;
+    BsdmmArgs u{};
+    u.X = c->X[j];
+    u.slab = slab_ref(c, j);
+    for (int i = 0; i < p.n_g[j]; ++i) { u.Z[i] = c->Zg[j][i]; u.U[i] = c->Ug[j][i]; u.prox_g[i] = to_dev(p.prox_g[j][i]); }
+    u.rows = c->rows[j];
+    u.K = (int)c->K;
+    u.j = j;
+    u.n_g = p.n_g[j];
+    u.prox_f = to_dev(p.prox_f[j]);
+    u.status = c->dstatus;
+    u.partials = c->partials;
+    return u;
+}
+static Bsdmm64Args bsdmm64_args(pmx_ctx* c, int j, int last_block) {
+    const pmx_bsdmm_params& p = c->bsd;
+    Bsdmm64Args u{};
+    u.X = c->Xd[j];
+    u.slab = c->slabd[j];
+    u.nslab = j == 0 ? c->nSlabA : c->nSlabS;
+    for (int i = 0; i < p.n_g[j]; ++i) { u.Z[i] = c->Zd[j][i]; u.U[i] = c->Ud[j][i]; u.prox_g[i] = to_dev(p.prox_g[j][i]); }
+    u.rows = c->rows[j];
+    u.K = (int)c->K;
+    u.j = j;
+    u.n_g = p.n_g[j];
+    u.prox_f = to_dev(p.prox_f[j]);
+    u.status = c->dstatus;
+    u.e_rel = p.e_rel[j];
+    u.e_abs = p.e_abs[j];
+    u.last_block = last_block;
+    return u;
+}
+// the Boyd test of block j over `size` entries (row-sharded: the global count; the caller adds comm_scalars);
+// last_block: end-of-iteration bookkeeping
+static BsdmmDecideArgs bsdmm_decide_args(pmx_ctx* c, int j, int64_t size, int last_block) {
+    const pmx_bsdmm_params& p = c->bsd;
+    BsdmmDecideArgs d{};
+    d.status = c->dstatus;
+    d.partials = c->partials;
+    d.j = j;
+    d.n_g = p.n_g[j];
+    d.size = size;
+    d.e_rel = p.e_rel[j];
+    d.e_abs = p.e_abs[j];
+    d.last_block = last_block;
+    return d;
+}
+
 static int bsdmm_enqueue_iteration(pmx_ctx* c) {
     const pmx_bsdmm_params& p = c->bsd;
     static const int default_order[2] = {0, 1};
@@ -3145,32 +3163,14 @@ static int bsdmm_enqueue_iteration(pmx_ctx* c) {
     const int* order = p.n_order > 0 ? p.order : default_order;
     for (int o = 0; o < n_order; ++o) {                                    // Gauss-Seidel in update_order, algorithms.py:805
         const int j = order[o];
+        const int last_block = o == n_order - 1;
         if (c->f64) {       // K1 tiles of block j + both step rules in one launch (k64_front), the block update by one workgroup
             int rc = enqueue_front64(c, c->Xd[0], c->Xd[1], j == 0, j == 1, true, true, 1.0);   // nmf.py:181-193
             if (rc != PMX_OK) return rc;
-            Bsdmm64Args u{};
-            u.X = c->Xd[j];
-            u.slab = c->slabd[j];
-            u.nslab = j == 0 ? c->nSlabA : c->nSlabS;
-            for (int i = 0; i < p.n_g[j]; ++i) { u.Z[i] = c->Zd[j][i]; u.U[i] = c->Ud[j][i]; u.prox_g[i] = to_dev(p.prox_g[j][i]); }
-            u.rows = c->rows[j];
-            u.K = (int)c->K;
-            u.j = j;
-            u.n_g = p.n_g[j];
-            u.prox_f = to_dev(p.prox_f[j]);
-            u.status = c->dstatus;
-            u.e_rel = p.e_rel[j];
-            u.e_abs = p.e_abs[j];
-            u.last_block = o == n_order - 1;
+            const Bsdmm64Args u = bsdmm64_args(c, j, last_block);
             if (c->f64big) {             // [r6] the update over the grid, its sums folded by the fp32 path's decide kernel (it only ever saw fp64 sums)
                 launch_bsdmm64b_update(u, c->partials, c->stream);
-                BsdmmDecideArgs d{};
-                d.status = c->dstatus; d.partials = c->partials;
-                d.j = j; d.n_g = p.n_g[j];
-                d.size = c->rows[j] * c->K;
-                d.e_rel = p.e_rel[j]; d.e_abs = p.e_abs[j];
-                d.last_block = u.last_block;
-                launch_bsdmm_decide(d, c->stream);
+                launch_bsdmm_decide(bsdmm_decide_args(c, j, c->rows[j] * c->K, last_block), c->stream);
             } else launch_bsdmm64_block(u, c->stream);
             HIP_CHECK(hipGetLastError());
             continue;
@@ -3180,39 +3180,20 @@ static int bsdmm_enqueue_iteration(pmx_ctx* c) {
         if (rc != PMX_OK) return rc;
         rc = enqueue_grad(c, c->X[0], c->X[1], j == 0, j == 1, c->absmax_by_finish);   // nmf.py:181-185 (only grads[j] is used)
         if (rc != PMX_OK) return rc;
-        BsdmmArgs u{};
+        BsdmmArgs u = bsdmm_args(c, j);
         // [r4] the partial Gram matrices of the new X_j from this launch (BsdmmArgs::gramPart): K <= 64, factors of <= 16384 rows
         // (cfg5); PMX_GRAM_IN_UPDATE=0 keeps k_gram_partial (A/B)
         const bool gram_here = c->gram_in_update && !eig_small_applies(c) && c->K <= 64 && gram_per(c->rows[j]) <= BSDMM_GRAM_ROWS;
         u.gramPart = gram_here ? c->gramPart : nullptr;
-        u.KP = c->KP;
+        u.KP = c->KP;                // (only this route fills it: the others leave gramPart, its one reader, at nullptr)
         c->gram_fresh[j] = gram_here;
-        u.X = c->X[j];
-        u.slab = slab_ref(c, j);
-        for (int i = 0; i < p.n_g[j]; ++i) { u.Z[i] = c->Zg[j][i]; u.U[i] = c->Ug[j][i]; u.prox_g[i] = to_dev(p.prox_g[j][i]); }
-        u.rows = c->rows[j];
-        u.K = (int)c->K;
-        u.j = j;
-        u.n_g = p.n_g[j];
-        u.prox_f = to_dev(p.prox_f[j]);
-        u.status = c->dstatus;
-        u.partials = c->partials;
         // this block's maxima for the fp16 K1 (the other block's are still those of the launch that last wrote it)
         u.absmax_out = k1_fp16(c->k1) ? c->absmax : nullptr;
         launch_bsdmm_update(u, c->stream);
         c->absmax_by_finish = u.absmax_out != nullptr;
-        BsdmmDecideArgs d{};
-        d.status = c->dstatus;
-        d.partials = c->partials;
-        d.j = j;
-        d.n_g = p.n_g[j];
-        d.size = c->rows[j] * c->K;
-        d.e_rel = p.e_rel[j];
-        d.e_abs = p.e_abs[j];
-        d.last_block = o == n_order - 1;
         // [r4] the test rides in the next step rule's k_gram_reduce launch (one launch less per block); pmx_bsdmm_run flushes the
         // last one of a chunk before it reads the status
-        c->bsd_decide = d;
+        c->bsd_decide = bsdmm_decide_args(c, j, c->rows[j] * c->K, last_block);
         c->bsd_decide_pending = true;
         HIP_CHECK(hipGetLastError());
     }
@@ -3226,10 +3207,8 @@ static int bsdmm_enqueue_iteration(pmx_ctx* c) {
 //   phase 2  the constraint updates with the user members' results taken from PMX_BUF_TG0 + .. (if any), the Boyd test of
 //            the block; last_block: end-of-iteration bookkeeping (iteration counter, stop when every block has converged)
 extern "C" int pmx_bsdmm_split(pmx_ctx* c, int j, int phase, int host_f, unsigned host_g, int last_block, double step_f_host, pmx_result* res) {
-    if (c) { c->absmax_by_finish = false; c->gram_by_update = false; }
-    int rc = require_ready(c);
+    int rc = begin_call(c, ALG_BSDMM, false);
     if (rc != PMX_OK) return rc;
-    if (c->algo != ALG_BSDMM) FAIL(PMX_E_STATE, "pmx_bsdmm_begin has not been called");
     if (j != 0 && j != 1) FAIL(PMX_E_INVALID, "block %d out of range", j);
     const pmx_bsdmm_params& p = c->bsd;
     if (host_g >> p.n_g[j]) FAIL(PMX_E_INVALID, "host_g names a constraint that does not exist");
@@ -3237,18 +3216,8 @@ extern "C" int pmx_bsdmm_split(pmx_ctx* c, int j, int phase, int host_f, unsigne
     // value from a user steps_f_cb must not fall through to the NMF rule of a context that may have no NMF gradient at all
     if (phase == 0 && !(step_f_host >= 0.0)) FAIL(PMX_E_INVALID, "block %d: the user step %g is not a positive number", j, step_f_host);
     auto args = [&](int stage) {
-        BsdmmArgs u{};
-        u.X = c->X[j];
-        u.slab = slab_ref(c, j);
-        for (int i = 0; i < p.n_g[j]; ++i) { u.Z[i] = c->Zg[j][i]; u.U[i] = c->Ug[j][i]; u.prox_g[i] = to_dev(p.prox_g[j][i]); u.T[i] = c->Tg[j][i]; }
-        u.rows = c->rows[j];
-        u.K = (int)c->K;
-        u.j = j;
-        u.n_g = p.n_g[j];
-        u.prox_f = to_dev(p.prox_f[j]);
-        u.status = c->dstatus;
-        u.partials = c->partials;
-        u.absmax_out = nullptr;
+        BsdmmArgs u = bsdmm_args(c, j);
+        for (int i = 0; i < p.n_g[j]; ++i) u.T[i] = c->Tg[j][i];
         u.stage = stage;
         u.host_f = host_f;
         u.host_g = host_g;
@@ -3284,16 +3253,7 @@ extern "C" int pmx_bsdmm_split(pmx_ctx* c, int j, int phase, int host_f, unsigne
             return PMX_OK;
         case 2: {
             if (host_g) launch_bsdmm_update(args(3), c->stream);
-            BsdmmDecideArgs d{};
-            d.status = c->dstatus;
-            d.partials = c->partials;
-            d.j = j;
-            d.n_g = p.n_g[j];
-            d.size = c->rows[j] * c->K;
-            d.e_rel = p.e_rel[j];
-            d.e_abs = p.e_abs[j];
-            d.last_block = last_block;
-            launch_bsdmm_decide(d, c->stream);
+            launch_bsdmm_decide(bsdmm_decide_args(c, j, c->rows[j] * c->K, last_block), c->stream);
             HIP_CHECK(hipGetLastError());
             rc = read_status(c);
             if (rc != PMX_OK) return rc;
@@ -3305,10 +3265,8 @@ extern "C" int pmx_bsdmm_split(pmx_ctx* c, int j, int phase, int host_f, unsigne
 }
 
 extern "C" int pmx_bsdmm_run(pmx_ctx* c, int n_iter, pmx_result* res) {
-    if (c) { c->absmax_by_finish = false; c->gram_by_update = false; }
-    int rc = require_ready(c, true);
+    int rc = begin_call(c, ALG_BSDMM, true);
     if (rc != PMX_OK) return rc;
-    if (c->algo != ALG_BSDMM) FAIL(PMX_E_STATE, "pmx_bsdmm_begin has not been called");
     if (n_iter < 0) FAIL(PMX_E_INVALID, "n_iter < 0");
     const int it0 = c->hstatus->it_done;
     c->gram_fresh[0] = c->gram_fresh[1] = false;     // (the caller may have touched the factors since the last call)
@@ -3503,27 +3461,16 @@ static int shard_post_split(pmx_ctx* c, int have_prev) {
 }
 
 extern "C" int pmx_adaprox_phase(pmx_ctx* c, int phase, int it, double b1_it, double b1_prev, int nsub) {
-    int rc = require_ready(c);
+    int rc = begin_call(c, ALG_ADAPROX, false, false);       // (absmax_by_finish is carried from one phase call to the next)
     if (rc != PMX_OK) return rc;
-    if (c->algo != ALG_ADAPROX) FAIL(PMX_E_STATE, "pmx_adaprox_begin has not been called");
     if (!c->comm) FAIL(PMX_E_STATE, "pmx_set_comm_buffer has not been called");
     const pmx_adaprox_params& p = c->ada;
-    for (int i = 0; i < p.prox[0].n; ++i) {
-        // A's proximal loop would need cross-rank sums per pass unless the operator is a coordinate-wise
-        // projection whose fixed point is reached in one pass (result independent of gamma)
-        const pmx_prox& q = p.prox[0].seq[i];
-        const bool box = q.op == PMX_PROX_ID || q.op == PMX_PROX_ZERO || q.op == PMX_PROX_PLUS ||
-                         ((q.op == PMX_PROX_MIN || q.op == PMX_PROX_MAX || q.op == PMX_PROX_HARD || q.op == PMX_PROX_HARD_PLUS) && !q.relative);
-        if (!box) FAIL(PMX_E_UNSUPPORTED, "row-sharded adaprox supports only projection-type prox_A (plus/id/zero/absolute min,max,hard)");
-    }
+    // A's proximal loop would need cross-rank sums per pass unless its operators are projections
+    if (!seq_is_projection(p.prox[0])) FAIL(PMX_E_UNSUPPORTED, "row-sharded adaprox supports only projection-type prox_A (plus/id/zero/absolute min,max,hard)");
     if (c->ssplit) {
         if (!c->comm_out) FAIL(PMX_E_STATE, "pmx_set_comm_out has not been called");
-        for (int i = 0; i < p.prox[1].n; ++i) {      // the same condition for S: its loop must not need a sum over all of S
-            const pmx_prox& q = p.prox[1].seq[i];
-            const bool box = q.op == PMX_PROX_ID || q.op == PMX_PROX_ZERO || q.op == PMX_PROX_PLUS ||
-                             ((q.op == PMX_PROX_MIN || q.op == PMX_PROX_MAX || q.op == PMX_PROX_HARD || q.op == PMX_PROX_HARD_PLUS) && !q.relative);
-            if (!box) FAIL(PMX_E_UNSUPPORTED, "S-split supports only projection-type prox_S; use the replicated S update");
-        }
+        // the same condition for S: its loop must not need a sum over all of S
+        if (!seq_is_projection(p.prox[1])) FAIL(PMX_E_UNSUPPORTED, "S-split supports only projection-type prox_S; use the replicated S update");
     }
     switch (phase) {
         case 0:
@@ -3550,9 +3497,7 @@ extern "C" int pmx_adaprox_phase(pmx_ctx* c, int phase, int it, double b1_it, do
             rc = ada_enqueue_moment(c, it, b1_it, b1_prev);
             c->shard_grad_from_comm = false;
             if (rc != PMX_OK) return rc;
-            const bool any_prox = p.prox[0].n > 0 || p.prox[1].n > 0;
-            const int ns = any_prox ? std::max(1, std::min(nsub, p.prox_max_iter)) : 0;
-            if (c->sub_nt != 1) c->sub_nt = ns <= 4 ? 4 : SUB_NT_MAX;   // fixed for this iteration (pmx_adaprox_more_subs continues with it)
+            const int ns = ada_pick_sub_batch(c, nsub);      // (passes per launch: fixed for this iteration, pmx_adaprox_more_subs continues with it)
             pmx_ctx::SubRec& r = c->sub_rec[it & 63];
             r.it = it; r.nt = c->sub_nt;
             r.enq = ada_enqueue_subs(c, 0, ns);
@@ -3567,38 +3512,18 @@ extern "C" int pmx_adaprox_phase(pmx_ctx* c, int phase, int it, double b1_it, do
 }
 
 static int pgm_enqueue_update(pmx_ctx* c, bool gS_from_comm, int check) {
-    const pmx_pgm_params& p = c->pgm;
-    PgmArgs u{};
-    for (int j = 0; j < 2; ++j) {            // S-split: block 1 is this rank's sncol columns of S (rows of S^T) only
-        u.X[j] = s_view(c, j, c->X[j]);
-        u.Xe[j] = s_view(c, j, p.accelerated ? c->Xe[j] : c->X[j]);
-        u.G[j] = s_view(c, j, c->G[j]);
-        u.slab[j] = slab_ref(c, j);
-        u.rows[j] = upd_rows(c, j);
-        u.prox[j] = to_dev(p.prox[j]);
-    }
-    if (gS_from_comm) { u.slab[1].base = c->ssplit ? c->comm_out : c->comm; u.slab[1].n = 1; u.slab[1].ld = (int)c->K; u.slab[1].extra = nullptr; }
-    u.K = (int)c->K;
-    u.status = c->dstatus;
-    u.partials = c->partials;
-    u.accelerated = p.accelerated;
+    PgmArgs u = pgm_args(c, true);
+    if (gS_from_comm) u.slab[1] = comm_slab(c);
     u.omega_next = next_omega(c);
     launch_pgm_update(u, c->stream);
-    DecideArgs d{};
-    d.status = c->dstatus;
-    d.partials = c->partials;
-    d.e_rel[0] = p.e_rel[0]; d.e_rel[1] = p.e_rel[1];
-    d.check = check;
-    launch_pgm_decide(d, c->stream);
+    enqueue_pgm_decide(c, check);
     HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }
 
 extern "C" int pmx_pgm_phase(pmx_ctx* c, int phase, int it) {
-    if (c) { c->absmax_by_finish = false; c->gram_by_update = false; }
-    int rc = require_ready(c);
+    int rc = begin_call(c, ALG_PGM, false);
     if (rc != PMX_OK) return rc;
-    if (c->algo != ALG_PGM) FAIL(PMX_E_STATE, "pmx_pgm_begin has not been called");
     if (!c->comm) FAIL(PMX_E_STATE, "pmx_set_comm_buffer has not been called");
     const pmx_pgm_params& p = c->pgm;
     if (p.bb_type || p.backtracking) FAIL(PMX_E_UNSUPPORTED, "row-sharded pgm supports the Lipschitz rule or fixed steps only");
@@ -3640,35 +3565,16 @@ extern "C" int pmx_pgm_phase(pmx_ctx* c, int phase, int it) {
 }
 
 static int bsdmm_enqueue_block(pmx_ctx* c, int j, bool gS_from_comm, const float* comm_scalars, int64_t size_global) {
-    const pmx_bsdmm_params& p = c->bsd;
-    BsdmmArgs u{};
-    u.X = c->X[j];
-    u.slab = slab_ref(c, j);
-    if (gS_from_comm) { u.slab.base = c->comm; u.slab.n = 1; u.slab.ld = (int)c->K; u.slab.extra = nullptr; }
-    for (int i = 0; i < p.n_g[j]; ++i) { u.Z[i] = c->Zg[j][i]; u.U[i] = c->Ug[j][i]; u.prox_g[i] = to_dev(p.prox_g[j][i]); }
-    u.rows = c->rows[j];
-    u.K = (int)c->K;
-    u.j = j;
-    u.n_g = p.n_g[j];
-    u.prox_f = to_dev(p.prox_f[j]);
-    u.status = c->dstatus;
-    u.partials = c->partials;
+    BsdmmArgs u = bsdmm_args(c, j);
+    // (the whole comm buffer even in an S-split context, unlike comm_slab(): row-sharded bsdmm replicates the S update)
+    if (gS_from_comm) u.slab = single_slab(c->comm, c->K, u.slab.stride);
     launch_bsdmm_update(u, c->stream);
     (void)comm_scalars; (void)size_global;
     HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }
 static int bsdmm_enqueue_decide(pmx_ctx* c, int j, const float* comm_scalars, int64_t size) {
-    const pmx_bsdmm_params& p = c->bsd;
-    BsdmmDecideArgs d{};
-    d.status = c->dstatus;
-    d.partials = c->partials;
-    d.j = j;
-    d.n_g = p.n_g[j];
-    d.size = size;
-    d.e_rel = p.e_rel[j];
-    d.e_abs = p.e_abs[j];
-    d.last_block = j == 1;
+    BsdmmDecideArgs d = bsdmm_decide_args(c, j, size, j == 1);
     d.comm_scalars = comm_scalars;
     launch_bsdmm_decide(d, c->stream);
     HIP_CHECK(hipGetLastError());
@@ -3676,10 +3582,8 @@ static int bsdmm_enqueue_decide(pmx_ctx* c, int j, const float* comm_scalars, in
 }
 
 extern "C" int pmx_bsdmm_phase(pmx_ctx* c, int phase) {
-    if (c) { c->absmax_by_finish = false; c->gram_by_update = false; }
-    int rc = require_ready(c);
+    int rc = begin_call(c, ALG_BSDMM, false);
     if (rc != PMX_OK) return rc;
-    if (c->algo != ALG_BSDMM) FAIL(PMX_E_STATE, "pmx_bsdmm_begin has not been called");
     if (!c->comm) FAIL(PMX_E_STATE, "pmx_set_comm_buffer has not been called");
     const pmx_bsdmm_params& p = c->bsd;
     const float* scal = c->comm + c->N * c->K + (int64_t)c->KP * c->KP + MAXK;
@@ -3759,9 +3663,8 @@ extern "C" int pmx_chain_status(pmx_ctx* c, int* halted, int* reason, int* it_do
 }
 
 extern "C" int pmx_adaprox_more_subs(pmx_ctx* c, int t0, int n) {
-    int rc = require_ready(c);
+    int rc = begin_call(c, ALG_ADAPROX, false, false);       // (absmax_by_finish is carried over, as in pmx_adaprox_phase)
     if (rc != PMX_OK) return rc;
-    if (c->algo != ALG_ADAPROX) FAIL(PMX_E_STATE, "pmx_adaprox_begin has not been called");
     rc = clear_halt(c);
     if (rc != PMX_OK) return rc;
     // Launches cover whole groups of `nt` passes, so the count really enqueued for the halted iteration is kept here
