@@ -14,6 +14,7 @@
 
 // GRAM_BLOCKS, gram_per, gram_nparts: pmx_common.h (the update kernels that leave partial Gram matrices behind use them too)
 constexpr int GRAM_THREADS = 256;
+constexpr int EIG_DEFL_STEPS = 16;       // power steps of the cold start's deflated check (eig_solve_block)
 // rows staged per LDS tile: all of a tile's requests go out before the first is used (a dependent round trip to memory
 // is ~1.3 us; with 32-row tiles a 128-row share took four of them and the kernel 18 us at 16384 x 64, now 7)
 template <int KP> constexpr int gram_chunk() { return KP == 128 ? 64 : 128; }
@@ -154,6 +155,7 @@ __device__ __forceinline__ void eig_solve_block(const EigArgs& a, const int f, c
     const int KP = a.KP, K = a.K, ld = KP + 1;
     const int t = threadIdx.x;
     // warm start (all-ones on the first call: the Perron vector of a non-negative Gram matrix is positive)
+    bool cold;
     {
         double v0 = (t < K) ? st->eigvec[f][t] : 0.0;
         double q = v0 * v0;
@@ -163,6 +165,7 @@ __device__ __forceinline__ void eig_solve_block(const EigArgs& a, const int f, c
         __syncthreads();
         const double n0 = sqrt(red[0] + red[1] + red[2] + red[3]);
         if (t < K) vec[t] = (n0 > 0.0 && n0 == n0 && n0 < 1e300) ? v0 / n0 : 1.0 / sqrt((double)K);
+        cold = !__syncthreads_or(t < K && v0 != 1.0);        // the all-ones start of a reset context (pmx_api.hip: reset_status)
     }
     __syncthreads();
     double lam_prev = -1.0, lam = 0.0;
@@ -303,14 +306,83 @@ __device__ __forceinline__ void eig_solve_block(const EigArgs& a, const int f, c
         }
         if (ud > 0.0) probe = fmax(probe, un / ud);
     }
-    const bool not_dominant = probe > l * (1.0 + 1e-5);
+    // ---- cold starts only: the all-ones start can be orthogonal to the dominant eigenvector TO THE LAST BIT (mixed-sign factors:
+    //      a dominant eigenvector +-1 / sqrt(K)); the iteration then settles on the second eigenvalue with a small residual, and with
+    //      a top gap of 1e-3 neither bound above is sharp enough to notice.  Sixteen power steps from a fixed vector without
+    //      structure, kept orthogonal to the accepted vector: if that vector is the second eigenvector these converge on the first
+    //      at the rate of the THIRD eigenvalue, and their Rayleigh quotient -- a lower bound on lmax like any other -- exceeds l.
+    //      A warm start carries rounding-level components of every eigenvector and is not checked (k_eig's time in a running
+    //      solver is unchanged). ---------------------------------------------------------------------------------------------------
+    double rho = 0.0;
+    if (cold && l > 0.0 && l == l && l < 1e300) {
+        if (t < K) { double r0 = (double)(t + 1) * 0.6180339887498949; wv[t] = r0 - floor(r0) - 0.37; }
+        __syncthreads();
+        for (int stepi = 0; stepi < EIG_DEFL_STEPS; ++stepi) {
+            double a2 = (t < K) ? wv[t] * vec[t] : 0.0, b2 = (t < K) ? vec[t] * vec[t] : 0.0;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) { a2 += __shfl_xor(a2, o); b2 += __shfl_xor(b2, o); }
+            __syncthreads();
+            if ((t & 63) == 0) { red[t >> 6] = a2; red[4 + (t >> 6)] = b2; }
+            __syncthreads();
+            const double pa = red[0] + red[1] + red[2] + red[3], pb = red[4] + red[5] + red[6] + red[7];
+            const double wt = (t < K) ? wv[t] - (pb > 0.0 ? pa / pb : 0.0) * vec[t] : 0.0;
+            __syncthreads();
+            if (t < K) wv[t] = wt;
+            __syncthreads();
+            double s2 = 0.0;
+            if (t < K) for (int k = 0; k < K; ++k) s2 += (double)g[k * ld + t] * wv[k];
+            double n1 = (t < K) ? s2 * wt : 0.0, d1 = (t < K) ? wt * wt : 0.0, c1 = (t < K) ? s2 * s2 : 0.0;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) { n1 += __shfl_xor(n1, o); d1 += __shfl_xor(d1, o); c1 += __shfl_xor(c1, o); }
+            __syncthreads();
+            if ((t & 63) == 0) { red[t >> 6] = n1; red[4 + (t >> 6)] = d1; eigred2[t >> 6] = c1; }
+            __syncthreads();
+            const double un = red[0] + red[1] + red[2] + red[3], ud = red[4] + red[5] + red[6] + red[7];
+            const double uc = eigred2[0] + eigred2[1] + eigred2[2] + eigred2[3];
+            __syncthreads();
+            if (!(ud > 0.0) || !(uc > 0.0)) break;          // (uniform)
+            rho = un / ud;
+            if (t < K) wv[t] = s2 / sqrt(uc);
+            __syncthreads();
+        }
+    }
+    // (fp64 contexts at size accept l at fp64 round-off: there the check is as sharp as the fp32 copy of G allows, and a doubt costs the exact solver)
+    const double rho_margin = a.force_exact == 2 ? 1e-9 : 1e-5;
+    const bool not_dominant = probe > l * (1.0 + 1e-5) || rho > l * (1.0 + rho_margin);
     int used_exact = 0;
-    if (l > 0.0 && l == l && l < 1e300 && (!(resid <= (a.force_exact == 2 ? 1e-9 : 1e-6) * l) || not_dominant || a.force_exact == 1)) {
+    // ---- The exact solver sees the Krylov space of its start vector only.  Started from the iterate (attempt 0) that is the whole
+    //      space unless the iterate lies in an invariant subspace EXACTLY -- which small-integer factors do produce: with every row
+    //      of the factor summing to zero G 1 = 0, the cold start is a null vector, the loop above leaves at nrm == 0 with l = 0 (and
+    //      used to hand out step = scale / 0 = inf for a non-zero matrix); with a block-diagonal G the iterate can stay inside the
+    //      block of the smaller eigenvalue for ever; an iterate that IS an eigenvector (all-ones under G = [[a, b], [b, a]]) ends the
+    //      recurrence after one step.  Attempt 1 runs the solver again from a fixed vector with no structure (a Weyl sequence) when
+    //      the first result violates the probe's lower bound on lmax, or when the recurrence ended before K steps; a larger
+    //      eigenvalue wins.  Every other call takes exactly the path it took before. ---------------------------------------------
+    int n_exact = K;                                     // dimension of the Krylov space attempt 0 saw
+    const bool run0 = l > 0.0 && l == l && l < 1e300 && (!(resid <= (a.force_exact == 2 ? 1e-9 : 1e-6) * l) || not_dominant || a.force_exact == 1);
+    for (int attempt = run0 ? 0 : 1; attempt < 2; ++attempt) {
+        if (attempt == 1 && !(probe > 0.0 && probe < 1e300 && (l <= 0.0 || (used_exact && (probe > l * (1.0 + 1e-5) || rho > l * (1.0 + rho_margin) || n_exact < K))))) break;    // (uniform)
+        const double l_in = l;                           // attempt 1 keeps the larger of the two
+        const double lscale = attempt == 0 ? l : fmax(l, fmax(probe, rho));
         // ---- Lanczos tridiagonalisation with full re-orthogonalisation (fp64), K steps = exact ---------
         __shared__ double al[MAXK], be[MAXK + 1], cdot[MAXK];
         __shared__ int nT;
         double* Q = a.Q + (int64_t)f * KP * KP;         // Q[j][*] = j-th Lanczos vector
-        if (t < K) Q[t] = vec[t];                        // q_0 = current iterate (unit norm)
+        if (attempt == 0) {
+            if (t < K) Q[t] = vec[t];                    // q_0 = current iterate (unit norm)
+        } else {
+            double r0 = 0.0;
+            if (t < K) { r0 = (double)(t + 1) * 0.6180339887498949; r0 = r0 - floor(r0) - 0.37; }
+            double q0 = r0 * r0;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) q0 += __shfl_xor(q0, o);
+            __syncthreads();
+            if ((t & 63) == 0) red[t >> 6] = q0;
+            __syncthreads();
+            const double n0 = sqrt(red[0] + red[1] + red[2] + red[3]);
+            __syncthreads();
+            if (t < K) Q[t] = r0 / n0;
+        }
         if (t == 0) { be[0] = 0.0; nT = K; }
         __syncthreads();
         for (int j = 0; j < K; ++j) {
@@ -348,7 +420,7 @@ __device__ __forceinline__ void eig_solve_block(const EigArgs& a, const int f, c
             const double beta = sqrt(red[0] + red[1] + red[2] + red[3]);
             __syncthreads();
             if (t == 0) be[j + 1] = beta;
-            if (j + 1 == K || !(beta > 1e-13 * l)) {      // invariant subspace reached (uniform)
+            if (j + 1 == K || !(beta > 1e-13 * lscale)) {      // invariant subspace reached (uniform)
                 if (t == 0) nT = j + 1;
                 break;
             }
@@ -357,6 +429,7 @@ __device__ __forceinline__ void eig_solve_block(const EigArgs& a, const int f, c
         }
         __syncthreads();
         const int n = nT;
+        if (attempt == 0) n_exact = n;
         // ---- largest eigenvalue of T(al, be) by Sturm-count multisection: 256 shifts per round ---------
         __shared__ double blo, bhi;
         __shared__ int firstFull;
@@ -396,7 +469,9 @@ __device__ __forceinline__ void eig_solve_block(const EigArgs& a, const int f, c
             __syncthreads();
         }
         l = 0.5 * (blo + bhi);
+        if (attempt == 1 && !(l > l_in * (1.0 + 1e-13) || l_in <= 0.0)) l = l_in;      // (the same eigenvalue again: the first result, bit for bit)
         used_exact = 1;
+        __syncthreads();
     }
     if (t == 0) {
         st->lam[f] = l;
@@ -443,7 +518,7 @@ struct EigWaveOps {
         return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), k), __builtin_amdgcn_readlane(__double2loint(v), k));
     }
 };
-struct EigWaveMain { double l, lam, vr, resid; int it; };
+struct EigWaveMain { double l, lam, vr, resid; int it; bool cold; };
 // t: lane (0 .. 63)
 template <int KM>
 __device__ __forceinline__ EigWaveMain eig_wave_main(const EigArgs& a, const int t, const double* G, const int GS, const float* g, const int ld, const int K, const double ev0) {
@@ -452,6 +527,7 @@ __device__ __forceinline__ EigWaveMain eig_wave_main(const EigArgs& a, const int
     const int tt = in ? t : 0;
     const double v0 = in ? ev0 : 0.0;
     const double n0 = sqrt(O::wsum(v0 * v0));
+    const bool cold = O::wsum((in && v0 != 1.0) ? 1.0 : 0.0) == 0.0;      // the all-ones start of a reset context
     double vr = in ? ((n0 > 0.0 && n0 == n0 && n0 < 1e300) ? v0 / n0 : 1.0 / sqrt((double)K)) : 0.0;
     double lam_prev = -1.0, lam = 0.0;
     int it = 0, calm = 0;
@@ -478,7 +554,7 @@ __device__ __forceinline__ EigWaveMain eig_wave_main(const EigArgs& a, const int
     if (!(lam == lam)) l = lam;
     const double r1 = in ? gv - l * vr : 0.0;
     const double resid = sqrt(O::wsum(r1 * r1) / (rq_d > 0.0 ? rq_d : 1.0));
-    return EigWaveMain{l, lam, vr, resid, it};
+    return EigWaveMain{l, lam, vr, resid, it, cold};
 }
 template <int KM>
 __device__ __forceinline__ double eig_wave_probe(const int t, const float* g, const int ld, const int K) {
@@ -509,11 +585,41 @@ __device__ __forceinline__ double eig_wave_probe(const int t, const float* g, co
     if (ud > 0.0) probe = fmax(probe, un / ud);
     return probe;
 }
+// eig_solve_block's check of a cold start: EIG_DEFL_STEPS power steps from a fixed vector, kept orthogonal to the accepted one -> their Rayleigh quotient
+template <int KM>
+__device__ __forceinline__ double eig_wave_deflated(const int t, const float* g, const int ld, const int K, const double vr) {
+    using O = EigWaveOps<KM>;
+    const bool in = t < K;
+    const int tt = in ? t : 0;
+    double w = 0.0;
+    if (in) { w = (double)(t + 1) * 0.6180339887498949; w = w - floor(w) - 0.37; }
+    const double pb = O::wsum(vr * vr);
+    double rho = 0.0;
+    for (int stepi = 0; stepi < EIG_DEFL_STEPS; ++stepi) {
+        const double pa = O::wsum(w * vr);
+        w = in ? w - (pb > 0.0 ? pa / pb : 0.0) * vr : 0.0;
+        double s2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < KM; ++k) s2 += (double)g[k * ld + tt] * O::bcast(w, k);
+        if (!in) s2 = 0.0;
+        const double un = O::wsum(s2 * w), ud = O::wsum(w * w), uc = O::wsum(s2 * s2);
+        if (!(ud > 0.0) || !(uc > 0.0)) break;              // (uniform)
+        rho = un / ud;
+        w = in ? s2 / sqrt(uc) : 0.0;
+    }
+    return rho;
+}
 // the verdict, by the lanes of the wave that ran eig_wave_main: accepted -> stored, else the caller runs the exact solver
-__device__ __forceinline__ bool eig_wave_verdict(const EigArgs& a, const int f, const int t, const int K, const EigWaveMain& m, const double probe) {
+template <int KM>
+__device__ __forceinline__ bool eig_wave_verdict(const EigArgs& a, const int f, const int t, const int K, const EigWaveMain& m, const double probe,
+                                                 const float* g, const int ld) {
     DevStatus* st = a.status;
     const bool not_dominant = probe > m.l * (1.0 + 1e-5);
-    const bool need_exact = m.l > 0.0 && m.l == m.l && m.l < 1e300 && (!(m.resid <= 1e-6 * m.l) || not_dominant || a.force_exact);
+    // (l <= 0 under a non-zero matrix: the start vector was a null vector -- eig_solve_block restarts from another one)
+    bool need_exact = (m.l > 0.0 && m.l == m.l && m.l < 1e300 && (!(m.resid <= 1e-6 * m.l) || not_dominant || a.force_exact)) ||
+                            (m.l <= 0.0 && probe > 0.0 && probe < 1e300);
+    if (!need_exact && m.cold && m.l > 0.0 && m.l < 1e300)      // (eig_solve_block: the cold start may be orthogonal to the dominant eigenvector)
+        need_exact = eig_wave_deflated<KM>(t, g, ld, K, m.vr) > m.l * (1.0 + 1e-5);
     if (!need_exact) {
         if (t == 0) {
             st->lam[f] = m.l;
@@ -530,7 +636,7 @@ __device__ __forceinline__ bool eig_wave_solve(const EigArgs& a, const int f, co
     const int t = threadIdx.x;
     const EigWaveMain m = eig_wave_main<KM>(a, t, G, GS, g, ld, K, ev0);
     const double probe = eig_wave_probe<KM>(t, g, ld, K);
-    return eig_wave_verdict(a, f, t, K, m, probe);
+    return eig_wave_verdict<KM>(a, f, t, K, m, probe, g, ld);
 }
 
 __global__ __launch_bounds__(256) void k_eig(EigArgs a) {
@@ -557,7 +663,7 @@ __global__ __launch_bounds__(256) void k_eig(EigArgs a) {
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_s_barrier();
         if (w == 0) {
-            const bool ok = eig_wave_verdict(a, f, lane, a.K, m, s_probe);
+            const bool ok = KP == 32 ? eig_wave_verdict<32>(a, f, lane, a.K, m, s_probe, g, ld) : eig_wave_verdict<64>(a, f, lane, a.K, m, s_probe, g, ld);
             if (lane == 0) s_accepted = ok;
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);

@@ -615,10 +615,12 @@ def test_full_size_gradient_against_subsampled_oracle(eng, mode):
 
 
 def test_lambda_max_after_an_eigenvalue_crossing(eng, orc):
-    """The power iteration is warm-started from the previous call's eigenvector.  Orthogonal columns make A^T A diagonal:
-    after the first call the iterate is exactly e_1; swap the column scales and e_1 is still an exact eigenvector -- of the
-    SMALLER eigenvalue now, zero residual.  The dominance probe (largest column norm / an independent Rayleigh quotient)
-    must send the call to the exact solver: a step from the second eigenvalue would be 4 x too long."""
+    """Three COLD starts on one context.  Orthogonal columns make A^T A diagonal; the column scales are swapped between the
+    calls, so the largest eigenvalue moves from e_1 to e_2.  This was written as a warm-start test (after the first call the
+    iterate is e_1, which the swap turns into an exact eigenvector of the SMALLER eigenvalue), but pmx_step_pgm resets a
+    context without a solver before every call (reset_status: nmf.step_pgm is a function of its arguments), so each of the
+    three calls starts from all-ones and none of them meets the crossing.  The warm start and the dominance probe that
+    guards it are pinned by tests/test_gpu_step_rule.py::test_warm_start_survives_a_crossing, inside pgm()."""
     M, N, K = 64, 48, 2
     rng = np.random.default_rng(0)
     Q, _ = np.linalg.qr(rng.standard_normal((M, K)))
