@@ -1,5 +1,6 @@
 // fp64 arithmetic at ANY size (K <= 128): the three back-ends of nmf() on fp64 operands, products and sums.
-// (included by pmx_api.hip after k_small_f64.hip, whose operator helpers and argument records it uses)
+// (included by pmx_api.hip after k_small_f64.hip, whose argument records and row helpers -- fold_slabs64, mom64_elem, bsdmm64_row -- it uses;
+// the operators are prox_row<double, NC> of k_update.hip)
 //
 // [r6] The reference computes in the dtype of its inputs (nmf.py:39-41) and every example it ships hands it fp64 arrays.
 // k_small_f64.hip covers the reference's own examples (K <= 16, M N <= 2^20); above that, fp64 callers were computed in fp32
@@ -24,11 +25,12 @@
 //                              against 8 KB of Y -- the HBM stream is ~20 % of its roof at K = 64.
 //   k64_gram_partial<KP> / k64_gram_reduce   the step rule's Gram matrices from fp64 rows (nmf.py:44-65), then k_eig with
 //                              EigArgs::force_exact = 2 (power steps on the fp64 matrix: lambda_max to fp64 round-off without the O(K^3) exact solver);
-//   k64b_pgm_update<NC>        k64_pgm_update for K <= 128 (a row = half a wave, NC = ceil(K / 32) values per lane);
+//   k64b_pgm_update<NC>        the pgm / FISTA update for K <= 128 (a row = half a wave, NC = ceil(K / 32) values per lane); the small-problem
+//                              route launches <1> on its own grid width (pmx_api.hip: pgm64_enqueue_iteration);
 //   k64b_bt_update / _bt_finish  the Beck-Teboulle line search's trial update and the next evaluation point (host-driven trials);
-//   k64b_bsdmm_update<NC>      k64_bsdmm_block spread over the grid + k_bsdmm_decide (the fp32 path's, it only ever saw fp64 sums);
+//   k64b_bsdmm_update<NC>      k64_bsdmm_block's row body (bsdmm64_row) spread over the grid + k_bsdmm_decide (the fp32 path's, it only ever saw fp64 sums);
 //   k64b_colsum / _alpha / _ada_moment / _ada_sub / _ada_finish / _ada_decide
-//                              k64_ada_iter as a chain of launches.  The proximal sub-iteration loop (algorithms.py:380-400)
+//                              k64_ada_iter as a chain of launches (the same mom64_elem).  The proximal sub-iteration loop (algorithms.py:380-400)
 //                              is one launch per pass; a pass first folds the previous pass's two sums and returns if the loop
 //                              has ended (DevStatus::sub_done, sub_tau).  The host enqueues a guess of passes; k64b_ada_finish
 //                              halts the chain (HALT_NEED_SUB, nothing written) when the loop needs more -- the host adds
@@ -130,38 +132,9 @@ void launch_gram64(const Gram64Args& a, int KP, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // rows of up to 128 fp64 values: half a wave per row, value c of lane l32 is component l32 + 32 c
 // ------------------------------------------------------------------------------------------------
-template <int NC>
-__device__ __forceinline__ void prox64b_row(double (&v)[NC], const bool (&ok)[NC], const ProxSeq& ps, const double (&sk)[NC]) {
-    for (int r = 0; r < ps.repeat; ++r)
-        for (int qi = 0; qi < ps.n; ++qi) {
-            const pmx_prox& p = ps.seq[qi];
-            if (p.op == PMX_PROX_UNITY || p.op == PMX_PROX_UNITY_PLUS) {          // operators.py:41-52 along the K components of the row
-                double s = 0.0;
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    if (p.op == PMX_PROX_UNITY_PLUS) v[c] = v[c] < 0.0 ? 0.0 : v[c];
-                    s += ok[c] ? v[c] : 0.0;
-                }
-                s = row_sum_d<32>(s);
-#pragma unroll
-                for (int c = 0; c < NC; ++c) v[c] = v[c] / s;                     // (no zero guard, like the reference)
-            } else {
-#pragma unroll
-                for (int c = 0; c < NC; ++c) v[c] = prox64_one<32>(v[c], ok[c], p, sk[c]);
-            }
-        }
-}
-template <int NC>
-__device__ __forceinline__ void fold_slabs64(double (&g)[NC], const bool (&ok)[NC], const double* slab, int nslab, int64_t rows, int K, int64_t r, int l32) {
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        g[c] = 0.0;
-        if (ok[c])
-            for (int qs = 0; qs < nslab; ++qs) g[c] += slab[((int64_t)qs * rows + r) * K + l32 + 32 * c];      // fixed order: slab 0, 1, 2, ...
-    }
-}
-
-// pgm / FISTA update (algorithms.py:93-108,130-135): grid (EW_BLOCKS, 2)
+// pgm / FISTA update (algorithms.py:93-108,130-135): grid (nbx, 2), nbx <= EW_BLOCKS; the partial-sum slots of idle workgroups stay zero.
+// nbx decides how the rows -- and with them the partial sums of the stopping test -- are dealt to workgroups: a small context
+// (K <= 16, M, N <= 8192) launches one half-wave per row of the longer factor, everything else EW_BLOCKS workgroups.
 template <int NC>
 __global__ __launch_bounds__(EW_THREADS) void k64b_pgm_update(Pgm64Args a) {
     __shared__ double scratch[2 * EW_WAVES];
@@ -187,7 +160,7 @@ __global__ __launch_bounds__(EW_THREADS) void k64b_pgm_update(Pgm64Args a) {
             const double xe = a.accelerated ? (ok[c] ? a.Xe[j][e] : 0.0) : xo[c];
             v[c] = xe - s * g[c];                                            // algorithms.py:107-108
         }
-        prox64b_row<NC>(v, ok, a.prox[j], sk);
+        prox_row<double, NC>(v, ok, a.prox[j], sk);
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             if (!ok[c]) continue;
@@ -203,13 +176,13 @@ __global__ __launch_bounds__(EW_THREADS) void k64b_pgm_update(Pgm64Args a) {
     double red[2] = {d2, n2};
     block_sum_store<2>(red, part_ptr(a.partials, SL_DIFF2, j) + blockIdx.x, (int64_t)2 * EW_BLOCKS, scratch);
 }
-void launch_pgm64b_update(const Pgm64Args& a, hipStream_t s) {
-    const dim3 grid(EW_BLOCKS, 2), block(EW_THREADS);
+void launch_pgm64b_update(const Pgm64Args& a, int nbx, hipStream_t s) {
+    const dim3 grid(nbx, 2), block(EW_THREADS);
     if (a.K <= 32) hipLaunchKernelGGL(k64b_pgm_update<1>, grid, block, 0, s, a);
     else if (a.K <= 64) hipLaunchKernelGGL(k64b_pgm_update<2>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(k64b_pgm_update<4>, grid, block, 0, s, a);
 }
-// gradient slabs -> G (pmx_grad)
+// gradient slabs -> G (pmx_grad, the line search); grid (nbx, 2): element-wise, any width gives the same bits
 __global__ __launch_bounds__(256) void k64b_fold(Fold64Args a) {
     const int j = blockIdx.y;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < a.count[j]; e += (int64_t)gridDim.x * 256) {
@@ -218,7 +191,7 @@ __global__ __launch_bounds__(256) void k64b_fold(Fold64Args a) {
         a.G[j][e] = g;
     }
 }
-void launch_fold64b(const Fold64Args& a, hipStream_t s) { hipLaunchKernelGGL(k64b_fold, dim3(1024, 2), dim3(256), 0, s, a); }
+void launch_fold64b(const Fold64Args& a, int nbx, hipStream_t s) { hipLaunchKernelGGL(k64b_fold, dim3(nbx, 2), dim3(256), 0, s, a); }
 
 // ------------------------------------------------------------------------------------------------
 // pgm with the Beck-Teboulle line search (algorithms.py:110-128) in fp64: the trial update of the blocks in `do_block`,
@@ -264,7 +237,7 @@ __global__ __launch_bounds__(EW_THREADS) void k64b_bt_update(Bt64Args a) {
             xp[c] = ok[c] ? a.Xp[j][e] : 0.0;
             v[c] = (ok[c] ? a.E[j][e] : 0.0) - ts * g[c];
         }
-        prox64b_row<NC>(v, ok, a.prox[j], sk);
+        prox_row<double, NC>(v, ok, a.prox[j], sk);
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             if (!ok[c]) continue;
@@ -325,58 +298,13 @@ __global__ __launch_bounds__(EW_THREADS) void k64b_bsdmm_update(Bsdmm64Args a, d
     const double w = a.n_g > 0 ? sf / sg : 0.0;
     const double nisg = a.n_g > 0 ? -1.0 / sg : 0.0;
     bool ok[NC];
-    double skf[NC], skg[NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) { ok[c] = l32 + 32 * c < K; skf[c] = sf; skg[c] = sg; }
+    for (int c = 0; c < NC; ++c) ok[c] = l32 + 32 * c < K;
     double red[2] = {0.0, 0.0}, redg[4 * PMX_MAX_G];
 #pragma unroll
     for (int i = 0; i < 4 * PMX_MAX_G; ++i) redg[i] = 0.0;
     const int64_t hw = ((int64_t)blockIdx.x * EW_THREADS + threadIdx.x) >> 5, nhw = ((int64_t)gridDim.x * EW_THREADS) >> 5;
-    for (int64_t r = hw; r < a.rows; r += nhw) {
-        double g[NC], xo[NC], v[NC];
-        fold_slabs64<NC>(g, ok, a.slab, a.nslab, a.rows, K, r, l32);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int64_t e = r * K + l32 + 32 * c;
-            xo[c] = ok[c] ? a.X[e] : 0.0;
-            double dx = 0.0;
-            for (int i = 0; i < a.n_g; ++i)                     // utils.py:330-336
-                if (ok[c]) dx += w * (xo[c] - a.Z[i][e] + a.U[i][e]);
-            v[c] = (xo[c] - dx) - sf * g[c];                    // utils.py:338 + nmf.py:185
-        }
-        prox64b_row<NC>(v, ok, a.prox_f, skf);
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-            if (ok[c]) {
-                a.X[r * K + l32 + 32 * c] = v[c];
-                const double d = v[c] - xo[c];
-                red[0] += d * d;
-                red[1] += v[c] * v[c];
-            }
-        for (int i = 0; i < a.n_g; ++i) {                       // do_the_mm, utils.py:295-304
-            double zo[NC], uo[NC], zn[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const int64_t e = r * K + l32 + 32 * c;
-                zo[c] = ok[c] ? a.Z[i][e] : 0.0;
-                uo[c] = ok[c] ? a.U[i][e] : 0.0;
-                zn[c] = v[c] + uo[c];
-            }
-            prox64b_row<NC>(zn, ok, a.prox_g[i], skg);
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-                if (ok[c]) {
-                    const int64_t e = r * K + l32 + 32 * c;
-                    const double rr = v[c] - zn[c], sd = nisg * (zn[c] - zo[c]), un = uo[c] + rr, us = un / sg;
-                    a.Z[i][e] = zn[c];
-                    a.U[i][e] = un;
-                    redg[4 * i + 0] += rr * rr;
-                    redg[4 * i + 1] += sd * sd;
-                    redg[4 * i + 2] += zn[c] * zn[c];
-                    redg[4 * i + 3] += us * us;
-                }
-        }
-    }
+    for (int64_t r = hw; r < a.rows; r += nhw) bsdmm64_row<NC, 32>(a, r, l32, ok, sf, sg, w, nisg, red, redg);
     block_sum_store<2>(red, part_ptr(partials, SL_DIFF2, j) + blockIdx.x, (int64_t)2 * EW_BLOCKS, scratch);
     __syncthreads();
     block_sum_store<4 * PMX_MAX_G>(redg, part_ptr(partials, SL_G0, j) + blockIdx.x, (int64_t)2 * EW_BLOCKS, scratch);
@@ -442,18 +370,6 @@ __global__ __launch_bounds__(256) void k64b_alpha(Ada64bArgs b) {
     }
     a.alpha_out[j * MAXK + k] = k >= a.K ? 0.0 : (a.use_fixed ? a.fixed[j] : (tsum / (double)a.rows[j]) / 10.0);
 }
-struct Mom64Scalars { double b1, b2, bias1, bias2, rho, rfac, xfac; };
-__device__ __forceinline__ Mom64Scalars mom64_scalars(const Ada64Args& a) {
-    Mom64Scalars m;
-    m.b1 = a.b1t; m.b2 = a.b2;
-    const double t = (double)(a.it + 1);
-    m.bias1 = 1.0 - pow(m.b1, t); m.bias2 = 1.0 - pow(m.b2, t);
-    const double rho_inf = 2.0 / (1.0 - m.b2) - 1.0;
-    m.rho = rho_inf - 2.0 * t * pow(m.b2, t) / (1.0 - pow(m.b2, t));
-    m.rfac = m.rho > 4.0 ? sqrt((m.rho - 4.0) * (m.rho - 2.0) * rho_inf / (rho_inf - 4.0) / (rho_inf - 2.0) / m.rho) : 1.0;
-    m.xfac = ((1.0 - m.b1) * (1.0 - m.b1)) / ((1.0 - a.b1prev) * (1.0 - a.b1prev));
-    return m;
-}
 // moments and update (algorithms.py:375-378), max Psi per workgroup; grid (EW_BLOCKS, 2)
 template <int NC>
 __global__ __launch_bounds__(EW_THREADS) void k64b_ada_moment(Ada64bArgs b) {
@@ -464,7 +380,6 @@ __global__ __launch_bounds__(EW_THREADS) void k64b_ada_moment(Ada64bArgs b) {
     const int K = a.K;
     const int64_t rows = a.rows[j];
     const Mom64Scalars ms = mom64_scalars(a);
-    const double b1 = ms.b1, b2 = ms.b2;
     double alpha[NC];
     bool ok[NC];
 #pragma unroll
@@ -477,39 +392,7 @@ __global__ __launch_bounds__(EW_THREADS) void k64b_ada_moment(Ada64bArgs b) {
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             if (!ok[c]) continue;
-            const int64_t e = r * K + l32 + 32 * c;
-            const double g = gg[c];
-            const double m = (1.0 - b1) * g + b1 * a.Mm[j][e];
-            const double v = (1.0 - b2) * (g * g) + b2 * a.Vv[j][e];
-            a.Mm[j][e] = m;
-            a.Vv[j][e] = v;
-            double phi, psi;
-            switch (a.scheme) {
-                case PMX_ADAM: phi = m / ms.bias1; psi = sqrt(v / ms.bias2) + a.eps; break;
-                case PMX_NADAM: phi = (b1 * m + (1.0 - b1) * g) / ms.bias1; psi = sqrt(v / ms.bias2) + a.eps; break;
-                case PMX_RADAM:
-                    phi = m / ms.bias1;
-                    psi = ms.rho > 4.0 ? sqrt(v / ms.bias2) / ms.rfac : 1.0;
-                    if (a.eps > 0.0) psi = fmax(psi, sqrt(a.eps));
-                    break;
-                default: {   // amsgrad / padam / adamx (algorithms.py:170-221)
-                    double cap = v;
-                    if (a.Vh[j] != nullptr) {
-                        const double old = a.Vh[j][e];
-                        cap = fmax(a.scheme == PMX_ADAMX ? ms.xfac * old : old, v);
-                        a.Vh[j][e] = cap;
-                    }
-                    if (a.eps > 0.0) cap = fmax(cap, a.eps);
-                    psi = a.scheme == PMX_PADAM ? pow(cap, a.p) : sqrt(cap);
-                    phi = m;
-                }
-            }
-            const double xo = a.X[j][e];
-            if (a.check_convergence) a.Xp[j][e] = xo;
-            const double xn = xo - alpha[c] * phi / psi;
-            a.X[j][e] = xn;
-            if (a.has_prox[j]) { a.Psi[j][e] = psi; a.z[j][e] = xn; }
-            maxpsi = nanmax(maxpsi, psi);
+            maxpsi = nanmax(maxpsi, mom64_elem(a, ms, j, r * K + l32 + 32 * c, gg[c], alpha[c]));
         }
     }
     double mv = wave_nanmax(maxpsi);
@@ -563,7 +446,7 @@ __global__ __launch_bounds__(EW_THREADS) void k64b_ada_sub(Ada64bArgs b) {
             const double x = ok[c] ? a.X[j][e] : 0.0, ps = ok[c] ? a.Psi[j][e] : 0.0;
             v[c] = zz[c] - rat[c] * ps * (zz[c] - x);
         }
-        prox64b_row<NC>(v, ok, a.prox[j], gamma);
+        prox_row<double, NC>(v, ok, a.prox[j], gamma);
 #pragma unroll
         for (int c = 0; c < NC; ++c)
             if (ok[c]) {

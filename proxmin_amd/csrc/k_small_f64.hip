@@ -11,11 +11,15 @@
 //                   with fp64 products (rows staged through LDS 256 at a time, thread = entry (i, j)), then k_eig_small's
 //                   own solve -- warm-started power iteration with an fp64 Rayleigh quotient, residual <= 1e-6 lambda,
 //                   dominance probes, exact Lanczos / Sturm fall-back (k_gram.hip) -- which was fp64 all along;
-//   k64_pgm_update  slab fold, X = prox(Xe - s G), FISTA extrapolation, the two sums of the stopping test
-//                   (algorithms.py:93-108,130-135), every operator of proxmin.operators on fp64 values;
+//   k64b_pgm_update<1>  (k_big_f64.hip, on this route's own grid width) slab fold, X = prox(Xe - s G), FISTA extrapolation, the
+//                   two sums of the stopping test (algorithms.py:93-108,130-135), every operator of proxmin.operators on fp64 values;
 //   k_pgm_decide    the stopping test (shared with the fp32 path: it only ever saw fp64 sums).
 // Not a fast path (no matrix cores at K <= 16, three launches, ~25 us per iteration at 200 x 1000 x 5): a parity path --
 // tests/test_gpu_f64.py holds it to rtol 1e-10 against the reference's own fp64 fixtures.
+// adaprox and bsdmm run as one single-workgroup launch per iteration / block update (k64_ada_iter<G>, k64_bsdmm_block<G> below).
+// What these share with the any-size kernels of k_big_f64.hip lives here, once: the argument records, fold_slabs64 (gradient slabs
+// of a row, fixed order), mom64_scalars / mom64_elem (the Adam-family moment update), bsdmm64_row (the row body of a block update).
+// The operators are prox_row<double, NC, G> of k_update.hip -- the same code the fp32 kernels instantiate for float.
 // ------------------------------------------------------------------------------------------------
 constexpr int S64_ROWS = 8;                  // rows of a K1 tile (16 in k_grad_small: the fp64 tile must fit the static LDS limit)
 
@@ -181,61 +185,6 @@ hipError_t launch_front64(const Grad64Args& ga, const EigArgs& ea, const double*
     return hipGetLastError();
 }
 
-// every operator of proxmin.operators on ONE fp64 value per lane (K <= 16: a row lives in lanes 0 .. K-1 of its 32)
-// -- prox_one (k_update.hip) restated for double, same expressions in the same order (operators.py:20-160)
-// sum over the G lanes that share a row (G = 32: a half-wave; 16 / 8: [r4] the single-workgroup adaprox / bsdmm kernels pack 2 / 4 rows
-// into a half-wave when K <= 16 / 8).  Lanes >= K hold zeros, so the 32-lane butterfly and the shorter ones give the same bits.
-template <int G>
-__device__ __forceinline__ double row_sum_d(double v) {
-    if (G > 16) v += swz16_d(v);
-    if (G > 8) v += __shfl_xor(v, 8);
-    v += __shfl_xor(v, 4);
-    v += dpp_d<DPP_XOR2>(v);
-    v += dpp_d<DPP_XOR1>(v);
-    return v;
-}
-template <int G = 32>
-__device__ __forceinline__ double prox64_one(double v, bool ok, const pmx_prox& p, double sk) {
-    switch (p.op) {
-        case PMX_PROX_ID: return v;
-        case PMX_PROX_ZERO: return 0.0;
-        case PMX_PROX_PLUS: return v < 0.0 ? 0.0 : v;
-        case PMX_PROX_UNITY:
-        case PMX_PROX_UNITY_PLUS: {
-            if (p.op == PMX_PROX_UNITY_PLUS) v = v < 0.0 ? 0.0 : v;
-            const double s = row_sum_d<G>(ok ? v : 0.0);
-            return v / s;                                   // (no zero guard, like the reference)
-        }
-        default: {
-            const double t = p.relative ? p.thresh * sk : p.thresh;
-            double x = v;
-            switch (p.op) {
-                case PMX_PROX_MIN: x = (x - t < 0.0) ? t : x; break;
-                case PMX_PROX_MAX: x = (x - t > 0.0) ? t : x; break;
-                case PMX_PROX_HARD: x = (fabs(x) < t) ? 0.0 : x; break;
-                case PMX_PROX_HARD_PLUS: x = (fabs(x) < t) ? 0.0 : x; x = x < 0.0 ? 0.0 : x; break;
-                case PMX_PROX_SOFT:
-                case PMX_PROX_SOFT_PLUS: {
-                    double m = fabs(x) - t;
-                    m = m < 0.0 ? 0.0 : m;
-                    const double sg = (double)(x > 0.0) - (double)(x < 0.0);
-                    x = sg * m;
-                    if (p.op == PMX_PROX_SOFT_PLUS) x = x < 0.0 ? 0.0 : x;
-                    break;
-                }
-                default: break;
-            }
-            return x;
-        }
-    }
-}
-template <int G = 32>
-__device__ __forceinline__ double prox64_row(double v, bool ok, const ProxSeq& ps, double sk) {
-    for (int r = 0; r < ps.repeat; ++r)
-        for (int q = 0; q < ps.n; ++q) v = prox64_one<G>(v, ok, ps.seq[q], sk);
-    return v;
-}
-
 struct Pgm64Args {
     double* X[2];
     double* Xe[2];           // extrapolated point (== X when not accelerated)
@@ -250,65 +199,30 @@ struct Pgm64Args {
     int accelerated;
     double omega_next;
 };
-// grid (workgroups, 2 blocks); half-wave = row as in k_pgm_update; idle workgroups of the partial-sum slots stay zero
-__global__ __launch_bounds__(EW_THREADS) void k64_pgm_update(Pgm64Args a) {
-    __shared__ double scratch[2 * EW_WAVES];
-    const int j = blockIdx.y;
-    const int halted = __builtin_nontemporal_load(&a.status->halt);
-    const double s = a.status->step[j];
-    if (halted) return;
-    const int64_t rows = a.rows[j];
-    const int K = a.K;
-    const int l32 = threadIdx.x & 31;
-    const bool ok = l32 < K;
-    double d2 = 0.0, n2 = 0.0;
-    const int64_t hw = ((int64_t)blockIdx.x * EW_THREADS + threadIdx.x) >> 5, nhw = ((int64_t)gridDim.x * EW_THREADS) >> 5;
-    for (int64_t r = hw; r < rows; r += nhw) {
-        const int64_t e = r * K + l32;
-        double g = 0.0;
-        if (ok)
-            for (int q = 0; q < a.nslab[j]; ++q) g += a.slab[j][(int64_t)q * rows * K + e];      // fixed order: slab 0, 1, 2, ...
-        const double xo = ok ? a.X[j][e] : 0.0;
-        const double xe = a.accelerated ? (ok ? a.Xe[j][e] : 0.0) : xo;
-        double v = xe - s * g;                                               // algorithms.py:107-108
-        v = prox64_row(v, ok, a.prox[j], s);
-        if (ok) {
-            a.X[j][e] = v;
-            a.G[j][e] = g;
-            if (a.accelerated) a.Xe[j][e] = v + a.omega_next * (v - xo);     // algorithms.py:93-95 of the next iteration
-            const double d = v - xo;
-            d2 += d * d;
-            n2 += v * v;
-        }
-    }
-    double red[2] = {d2, n2};
-    block_sum_store<2>(red, part_ptr(a.partials, SL_DIFF2, j) + blockIdx.x, (int64_t)2 * EW_BLOCKS, scratch);
-}
-void launch_pgm64_update(const Pgm64Args& a, int nbx, hipStream_t s) { hipLaunchKernelGGL(k64_pgm_update, dim3(nbx, 2), dim3(EW_THREADS), 0, s, a); }
-
-// fold of the gradient slabs alone (pmx_grad in an fp64 context)
+// fold of the gradient slabs alone (pmx_grad in an fp64 context: k64b_fold, k_big_f64.hip)
 struct Fold64Args {
     const double* slab[2];
     int nslab[2];
     double* G[2];
     int64_t count[2];
 };
-__global__ __launch_bounds__(256) void k64_fold(Fold64Args a) {
-    const int j = blockIdx.y;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < a.count[j]; e += (int64_t)gridDim.x * 256) {
-        double g = 0.0;
-        for (int q = 0; q < a.nslab[j]; ++q) g += a.slab[j][(int64_t)q * a.count[j] + e];
-        a.G[j][e] = g;
+// the gradient of row r from its slabs: value c of lane l is component l + 32 c (NC = 1: any lane group up to 32 wide)
+template <int NC>
+__device__ __forceinline__ void fold_slabs64(double (&g)[NC], const bool (&ok)[NC], const double* slab, int nslab, int64_t rows, int K, int64_t r, int l32) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        g[c] = 0.0;
+        if (ok[c])
+            for (int qs = 0; qs < nslab; ++qs) g[c] += slab[((int64_t)qs * rows + r) * K + l32 + 32 * c];      // fixed order: slab 0, 1, 2, ...
     }
 }
-void launch_fold64(const Fold64Args& a, hipStream_t s) { hipLaunchKernelGGL(k64_fold, dim3(64, 2), dim3(256), 0, s, a); }
 
 // ------------------------------------------------------------------------------------------------
 // [r4] adaprox in fp64 (small problems): the whole tail of an iteration (algorithms.py:369-410, nmf.py:91-93) by ONE workgroup.
 // Half-wave = row (K <= 16 lanes of its 32 active), the 32 half-waves of the workgroup stride over the rows; every sum over a
 // block is a wave tree + a 16-term serial sum in LDS, the same for every thread.  State (X, X_, M, V, Vhat, Psi, z) in global
 // memory -- <= 1 MB per array, L2-resident.  Not a fast path (a proximal pass over 8192 rows is 256 trips of the loop): the parity
-// path for fp64 callers of adaprox, as k64_pgm_update is for pgm.
+// path for fp64 callers of adaprox, as k64b_pgm_update on one half-wave per row is for pgm.
 // ------------------------------------------------------------------------------------------------
 struct Ada64Args {
     double* X[2];
@@ -334,6 +248,56 @@ struct Ada64Args {
     double fixed[2];
     double* alpha_out;       // [2][16]: the steps this iteration used (pmx_step_adaprox in an fp64 context reads them)
 };
+// scalars of the moment schemes (algorithms.py:147-245), all in fp64
+struct Mom64Scalars { double b1, b2, bias1, bias2, rho, rfac, xfac; };
+__device__ __forceinline__ Mom64Scalars mom64_scalars(const Ada64Args& a) {
+    Mom64Scalars m;
+    m.b1 = a.b1t; m.b2 = a.b2;
+    const double t = (double)(a.it + 1);
+    m.bias1 = 1.0 - pow(m.b1, t); m.bias2 = 1.0 - pow(m.b2, t);
+    const double rho_inf = 2.0 / (1.0 - m.b2) - 1.0;
+    m.rho = rho_inf - 2.0 * t * pow(m.b2, t) / (1.0 - pow(m.b2, t));
+    m.rfac = m.rho > 4.0 ? sqrt((m.rho - 4.0) * (m.rho - 2.0) * rho_inf / (rho_inf - 4.0) / (rho_inf - 2.0) / m.rho) : 1.0;
+    m.xfac = ((1.0 - m.b1) * (1.0 - m.b1)) / ((1.0 - a.b1prev) * (1.0 - a.b1prev));
+    return m;
+}
+// moments and update of entry e of block j from its gradient g (algorithms.py:375-378): M, V, (Vhat,) X, X_, Psi, z; returns Psi.
+// The one fp64 copy, for k64_ada_iter and k64b_ada_moment.  (The fp32 moment_elem is NOT this in another type: it mixes fp32
+// and fp64 the way NumPy's weak scalars do -- k_update.hip.)
+__device__ __forceinline__ double mom64_elem(const Ada64Args& a, const Mom64Scalars& ms, int j, int64_t e, double g, double alpha) {
+    const double b1 = ms.b1, b2 = ms.b2;
+    const double m = (1.0 - b1) * g + b1 * a.Mm[j][e];
+    const double v = (1.0 - b2) * (g * g) + b2 * a.Vv[j][e];
+    a.Mm[j][e] = m;
+    a.Vv[j][e] = v;
+    double phi, psi;
+    switch (a.scheme) {
+        case PMX_ADAM: phi = m / ms.bias1; psi = sqrt(v / ms.bias2) + a.eps; break;
+        case PMX_NADAM: phi = (b1 * m + (1.0 - b1) * g) / ms.bias1; psi = sqrt(v / ms.bias2) + a.eps; break;
+        case PMX_RADAM:
+            phi = m / ms.bias1;
+            psi = ms.rho > 4.0 ? sqrt(v / ms.bias2) / ms.rfac : 1.0;
+            if (a.eps > 0.0) psi = fmax(psi, sqrt(a.eps));
+            break;
+        default: {   // amsgrad / padam / adamx (algorithms.py:170-221)
+            double cap = v;
+            if (a.Vh[j] != nullptr) {
+                const double old = a.Vh[j][e];
+                cap = fmax(a.scheme == PMX_ADAMX ? ms.xfac * old : old, v);
+                a.Vh[j][e] = cap;
+            }
+            if (a.eps > 0.0) cap = fmax(cap, a.eps);
+            psi = a.scheme == PMX_PADAM ? pow(cap, a.p) : sqrt(cap);
+            phi = m;
+        }
+    }
+    const double xo = a.X[j][e];
+    if (a.check_convergence) a.Xp[j][e] = xo;
+    const double xn = xo - alpha * phi / psi;
+    a.X[j][e] = xn;
+    if (a.has_prox[j]) { a.Psi[j][e] = psi; a.z[j][e] = xn; }
+    return psi;
+}
 template <int NV>
 __device__ __forceinline__ void wg_sum(double (&v)[NV], double* sm /* >= NV * EW_WAVES */) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -381,13 +345,8 @@ __global__ __launch_bounds__(EW_THREADS) void k64_ada_iter(Ada64Args a) {
         }
     }
     __syncthreads();
-    // ---- scalars of the moment schemes (algorithms.py:147-245), all in fp64
-    const double b1 = a.b1t, b2 = a.b2, t = (double)(a.it + 1);
-    const double bias1 = 1.0 - pow(b1, t), bias2 = 1.0 - pow(b2, t);
-    const double rho_inf = 2.0 / (1.0 - b2) - 1.0;
-    const double rho = rho_inf - 2.0 * t * pow(b2, t) / (1.0 - pow(b2, t));
-    const double rfac = rho > 4.0 ? sqrt((rho - 4.0) * (rho - 2.0) * rho_inf / (rho_inf - 4.0) / (rho_inf - 2.0) / rho) : 1.0;
-    const double xfac = ((1.0 - b1) * (1.0 - b1)) / ((1.0 - a.b1prev) * (1.0 - a.b1prev));
+    const Mom64Scalars ms = mom64_scalars(a);
+    const bool ok1[1] = {ok};
     int taus[2] = {0, 0};
     for (int j = 0; j < 2; ++j) {
         const int64_t rows = a.rows[j];
@@ -397,39 +356,9 @@ __global__ __launch_bounds__(EW_THREADS) void k64_ada_iter(Ada64Args a) {
         double maxpsi = -1.0;
         for (int64_t r = hw; r < rows; r += NG) {
             if (!ok) continue;
-            const int64_t e = r * K + l32;
-            double g = 0.0;
-            for (int q = 0; q < a.nslab[j]; ++q) g += a.slab[j][(int64_t)q * rows * K + e];      // fixed order: slab 0, 1, 2, ...
-            const double m = (1.0 - b1) * g + b1 * a.Mm[j][e];
-            const double v = (1.0 - b2) * (g * g) + b2 * a.Vv[j][e];
-            a.Mm[j][e] = m;
-            a.Vv[j][e] = v;
-            double phi, psi;
-            switch (a.scheme) {
-                case PMX_ADAM: phi = m / bias1; psi = sqrt(v / bias2) + a.eps; break;
-                case PMX_NADAM: phi = (b1 * m + (1.0 - b1) * g) / bias1; psi = sqrt(v / bias2) + a.eps; break;
-                case PMX_RADAM:
-                    phi = m / bias1;
-                    psi = rho > 4.0 ? sqrt(v / bias2) / rfac : 1.0;
-                    if (a.eps > 0.0) psi = fmax(psi, sqrt(a.eps));
-                    break;
-                default: {   // amsgrad / padam / adamx (algorithms.py:170-221)
-                    double cap = v;
-                    if (a.Vh[j] != nullptr) {
-                        const double old = a.Vh[j][e];
-                        cap = fmax(a.scheme == PMX_ADAMX ? xfac * old : old, v);
-                        a.Vh[j][e] = cap;
-                    }
-                    if (a.eps > 0.0) cap = fmax(cap, a.eps);
-                    psi = a.scheme == PMX_PADAM ? pow(cap, a.p) : sqrt(cap);
-                    phi = m;
-                }
-            }
-            const double xo = X[e];
-            if (a.check_convergence) a.Xp[j][e] = xo;
-            X[e] = xo - alpha * phi / psi;
-            if (a.has_prox[j]) { a.Psi[j][e] = psi; a.z[j][e] = X[e]; }
-            maxpsi = nanmax(maxpsi, psi);
+            double g[1];
+            fold_slabs64<1>(g, ok1, a.slab[j], a.nslab[j], rows, K, r, l32);
+            maxpsi = nanmax(maxpsi, mom64_elem(a, ms, j, r * K + l32, g[0], alpha));
         }
         // ---- the proximal sub-iterations (algorithms.py:380-400)
         if (a.has_prox[j]) {
@@ -441,19 +370,20 @@ __global__ __launch_bounds__(EW_THREADS) void k64_ada_iter(Ada64Args a) {
             for (int q = 1; q < EW_WAVES; ++q) mp = nanmax(mp, sm[q]);
             const double gamma = alpha / mp;                  // :384
             const double rat = gamma / alpha;                 // NaN if alpha == 0, as in the reference
+            const double gam1[1] = {gamma};
             int tau = 0;
             for (tau = 1; tau <= a.prox_max_iter; ++tau) {
                 double red[2] = {0.0, 0.0};
                 for (int64_t r = hw; r < rows; r += NG) {     // (whole half-waves take or skip a row: the row sums of prox_unity* need all lanes)
                     const int64_t e = r * K + l32;
                     const double zz = ok ? a.z[j][e] : 0.0, x = ok ? X[e] : 0.0, ps = ok ? a.Psi[j][e] : 0.0;
-                    double v = zz - rat * ps * (zz - x);
-                    v = prox64_row<G>(v, ok, a.prox[j], gamma);
+                    double v[1] = {zz - rat * ps * (zz - x)};
+                    prox_row<double, 1, G>(v, ok1, a.prox[j], gam1);
                     if (ok) {
-                        const double d = v - zz;
+                        const double d = v[0] - zz;
                         red[0] += d * d;
                         red[1] += zz * zz;
-                        a.z[j][e] = v;
+                        a.z[j][e] = v[0];
                     }
                 }
                 wg_sum<2>(red, sm);
@@ -524,10 +454,64 @@ struct Bsdmm64Args {
     double e_rel, e_abs;
     int last_block;
 };
+// one row of a block update: value c of lane l (of the G that share row r) is component l + G c.  dX, X = prox_f(..), then Z_i / U_i
+// of every constraint; the 2 + 4 n_g sums of the residual norms go to red2 / redg.  k64_bsdmm_block: NC = 1, G lanes per row;
+// k64b_bsdmm_update (k_big_f64.hip): NC values per lane, G = 32.
+template <int NC, int G>
+__device__ __forceinline__ void bsdmm64_row(const Bsdmm64Args& a, int64_t r, int l, const bool (&ok)[NC], double sf, double sg, double w, double nisg,
+                                            double (&red2)[2], double (&redg)[4 * PMX_MAX_G]) {
+    const int K = a.K;
+    double skf[NC], skg[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) { skf[c] = sf; skg[c] = sg; }
+    double g[NC], xo[NC], v[NC];
+    fold_slabs64<NC>(g, ok, a.slab, a.nslab, a.rows, K, r, l);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int64_t e = r * K + l + G * c;
+        xo[c] = ok[c] ? a.X[e] : 0.0;
+        double dx = 0.0;
+        for (int i = 0; i < a.n_g; ++i)                         // utils.py:330-336
+            if (ok[c]) dx += w * (xo[c] - a.Z[i][e] + a.U[i][e]);
+        v[c] = (xo[c] - dx) - sf * g[c];                        // utils.py:338 + nmf.py:185
+    }
+    prox_row<double, NC, G>(v, ok, a.prox_f, skf);
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        if (ok[c]) {
+            a.X[r * K + l + G * c] = v[c];
+            const double d = v[c] - xo[c];
+            red2[0] += d * d;
+            red2[1] += v[c] * v[c];
+        }
+    for (int i = 0; i < a.n_g; ++i) {                           // do_the_mm, utils.py:295-304
+        double zo[NC], uo[NC], zn[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int64_t e = r * K + l + G * c;
+            zo[c] = ok[c] ? a.Z[i][e] : 0.0;
+            uo[c] = ok[c] ? a.U[i][e] : 0.0;
+            zn[c] = v[c] + uo[c];
+        }
+        prox_row<double, NC, G>(zn, ok, a.prox_g[i], skg);
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+            if (ok[c]) {
+                const int64_t e = r * K + l + G * c;
+                const double rr = v[c] - zn[c], sd = nisg * (zn[c] - zo[c]), un = uo[c] + rr, us = un / sg;
+                a.Z[i][e] = zn[c];
+                a.U[i][e] = un;
+                redg[4 * i + 0] += rr * rr;
+                redg[4 * i + 1] += sd * sd;
+                redg[4 * i + 2] += zn[c] * zn[c];
+                redg[4 * i + 3] += us * us;
+            }
+    }
+}
 template <int G>
 __global__ __launch_bounds__(EW_THREADS) void k64_bsdmm_block(Bsdmm64Args a) {
     constexpr int NG = EW_THREADS / G;
-    __shared__ double sm[(2 + 4 * PMX_MAX_G) * EW_WAVES];
+    __shared__ double sm[4 * PMX_MAX_G * EW_WAVES];
     DevStatus* st = a.status;
     if (chain_halted(st)) return;
     const int tid = threadIdx.x, l32 = tid % G, hw = tid / G;
@@ -537,42 +521,14 @@ __global__ __launch_bounds__(EW_THREADS) void k64_bsdmm_block(Bsdmm64Args a) {
     const double sg = sf * 1.0 * 2.0 * (double)a.n_g;          // get_step_g (utils.py:269-279), identity L
     const double w = a.n_g > 0 ? sf / sg : 0.0;                // step_f / step_g[i]
     const double nisg = a.n_g > 0 ? -1.0 / sg : 0.0;
-    double red[2 + 4 * PMX_MAX_G];
+    const bool ok1[1] = {ok};
+    double red[2] = {0.0, 0.0}, redg[4 * PMX_MAX_G];
 #pragma unroll
-    for (int i = 0; i < 2 + 4 * PMX_MAX_G; ++i) red[i] = 0.0;
-    for (int64_t r = hw; r < a.rows; r += NG) {                // (whole half-waves take or skip a row: prox_unity* sums over its lanes)
-        const int64_t e = r * K + l32;
-        double g = 0.0;
-        if (ok)
-            for (int q = 0; q < a.nslab; ++q) g += a.slab[(int64_t)q * a.rows * K + e];
-        const double xo = ok ? a.X[e] : 0.0;
-        double dx = 0.0;
-        for (int i = 0; i < a.n_g; ++i)                         // utils.py:330-336
-            if (ok) dx += w * (xo - a.Z[i][e] + a.U[i][e]);
-        double v = (xo - dx) - sf * g;                          // utils.py:338 + nmf.py:185
-        v = prox64_row<G>(v, ok, a.prox_f, sf);
-        if (ok) {
-            a.X[e] = v;
-            const double d = v - xo;
-            red[0] += d * d;
-            red[1] += v * v;
-        }
-        for (int i = 0; i < a.n_g; ++i) {                       // do_the_mm, utils.py:295-304
-            const double zo = ok ? a.Z[i][e] : 0.0, uo = ok ? a.U[i][e] : 0.0;
-            double zn = v + uo;
-            zn = prox64_row<G>(zn, ok, a.prox_g[i], sg);
-            if (ok) {
-                const double rr = v - zn, sd = nisg * (zn - zo), un = uo + rr, us = un / sg;
-                a.Z[i][e] = zn;
-                a.U[i][e] = un;
-                red[2 + 4 * i + 0] += rr * rr;
-                red[2 + 4 * i + 1] += sd * sd;
-                red[2 + 4 * i + 2] += zn * zn;
-                red[2 + 4 * i + 3] += us * us;
-            }
-        }
-    }
-    wg_sum<2 + 4 * PMX_MAX_G>(red, sm);
+    for (int i = 0; i < 4 * PMX_MAX_G; ++i) redg[i] = 0.0;
+    for (int64_t r = hw; r < a.rows; r += NG)                  // (whole half-waves take or skip a row: prox_unity* sums over its lanes)
+        bsdmm64_row<1, G>(a, r, l32, ok1, sf, sg, w, nisg, red, redg);
+    wg_sum<2>(red, sm);
+    wg_sum<4 * PMX_MAX_G>(redg, sm);
     if (tid == 0) {     // check_constraint_convergence (utils.py:349-391) and end-of-iteration bookkeeping
         const double sq = sqrt((double)(a.rows * K));
         int conv = 1;
@@ -582,9 +538,9 @@ __global__ __launch_bounds__(EW_THREADS) void k64_bsdmm_block(Bsdmm64Args a) {
             conv = (0.0 <= e_pri) && (sqrt(red[0]) <= e_dual);
         } else {
             for (int i = 0; i < a.n_g; ++i) {
-                const double lR = sqrt(red[2 + 4 * i + 0]), lS = sqrt(red[2 + 4 * i + 1]);
-                const double e_pri = sq * a.e_abs + a.e_rel * fmax(sqrt(red[1]), sqrt(red[2 + 4 * i + 2]));
-                const double e_dual = sq * a.e_abs + a.e_rel * sqrt(red[2 + 4 * i + 3]);
+                const double lR = sqrt(redg[4 * i + 0]), lS = sqrt(redg[4 * i + 1]);
+                const double e_pri = sq * a.e_abs + a.e_rel * fmax(sqrt(red[1]), sqrt(redg[4 * i + 2]));
+                const double e_dual = sq * a.e_abs + a.e_rel * sqrt(redg[4 * i + 3]);
                 conv &= (lR <= e_pri) && (lS <= e_dual);
             }
         }

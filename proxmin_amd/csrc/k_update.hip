@@ -15,6 +15,7 @@
 // Control flow lives on the device: every kernel first reads DevStatus::halt (set by a single-block
 // "decide" kernel when the run converged or needs more proximal sub-iterations than were enqueued)
 // and becomes a no-op once it is set; the host enqueues chains of iterations without synchronising.
+#include <type_traits>
 #include "pmx_common.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -40,20 +41,32 @@ constexpr int SWZ_XOR16 = (0x10 << 10) | 0x1f;                                  
 // Row sums keep the butterfly order 16, 8, 4, 2, 1 (the association the parity fixtures were pinned with): the
 // three long strides as swizzles, the two short ones as DPP quad permutes.
 constexpr int SWZ_XOR8 = (0x08 << 10) | 0x1f, SWZ_XOR4 = (0x04 << 10) | 0x1f;
-__device__ __forceinline__ float row_sum32(float v) {   // sum over the 32 lanes that share a row
-    v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), SWZ_XOR16));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), SWZ_XOR8));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), SWZ_XOR4));
-    v += dpp_f<DPP_XOR2>(v);
-    v += dpp_f<DPP_XOR1>(v);
-    return v;
-}
-
 __device__ __forceinline__ double swz16_d(double v) {
     const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
     const unsigned lo = (unsigned)__builtin_amdgcn_ds_swizzle((int)(unsigned)u, SWZ_XOR16);
     const unsigned hi = (unsigned)__builtin_amdgcn_ds_swizzle((int)(unsigned)(u >> 32), SWZ_XOR16);
     return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+// sum over the G lanes that share a row.  float: G = 32 (half a wave).  double: G = 32, or 16 / 8 where the single-workgroup fp64
+// kernels (k_small_f64.hip) pack 2 / 4 rows of K <= 16 / 8 into a half-wave; lanes >= K hold zeros, so the 32-lane butterfly and
+// the shorter ones give the same bits.
+template <class T, int G>
+__device__ __forceinline__ T row_sum(T v) {
+    if constexpr (std::is_same<T, float>::value) {
+        static_assert(G == 32, "fp32 rows are 32 lanes wide");
+        v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), SWZ_XOR16));
+        v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), SWZ_XOR8));
+        v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), SWZ_XOR4));
+        v += dpp_f<DPP_XOR2>(v);
+        v += dpp_f<DPP_XOR1>(v);
+    } else {
+        if (G > 16) v += swz16_d(v);
+        if (G > 8) v += __shfl_xor(v, 8);
+        v += __shfl_xor(v, 4);
+        v += dpp_d<DPP_XOR2>(v);
+        v += dpp_d<DPP_XOR1>(v);
+    }
+    return v;
 }
 __device__ __forceinline__ double wave_sum(double v) {
     v += dpp_d<DPP_XOR1>(v);
@@ -192,31 +205,33 @@ __device__ __forceinline__ double fold_partials_nanmax_wt(const double* part) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// proximal operators on one row held across 32 lanes          (proxmin/operators.py:20-160)
-// v[c] is component l32 + 32c; ok[c] says whether that component exists (< K).
+// proximal operators on one row held across G lanes          (proxmin/operators.py:20-160)
+// The ONE implementation: T = float (NC values per lane, G = 32) for the fp32 kernels, T = double for k_big_f64.hip (the same
+// layout) and k_small_f64.hip (NC = 1, G = 8 / 16 / 32 lanes per row).
+// v[c] is component l + G c of the row; ok[c] says whether that component exists (< K).
 // sk[c] is the step the solver passes for that component (scalar steps: all equal).
 // ------------------------------------------------------------------------------------------------
-template <int NC>
-__device__ __forceinline__ void prox_one(float (&v)[NC], const bool (&ok)[NC], const pmx_prox& p, const float (&sk)[NC]) {
+template <class T, int NC, int G = 32>
+__device__ __forceinline__ void prox_one(T (&v)[NC], const bool (&ok)[NC], const pmx_prox& p, const T (&sk)[NC]) {
     switch (p.op) {
         case PMX_PROX_ID: break;
         case PMX_PROX_ZERO:
 #pragma unroll
-            for (int c = 0; c < NC; ++c) v[c] = 0.f;
+            for (int c = 0; c < NC; ++c) v[c] = (T)0;
             break;
         case PMX_PROX_PLUS:                                     // X[X<0] = 0
 #pragma unroll
-            for (int c = 0; c < NC; ++c) v[c] = v[c] < 0.f ? 0.f : v[c];
+            for (int c = 0; c < NC; ++c) v[c] = v[c] < (T)0 ? (T)0 : v[c];
             break;
         case PMX_PROX_UNITY:
         case PMX_PROX_UNITY_PLUS: {                             // X / sum(X, axis)   (no zero guard)
-            float s = 0.f;
+            T s = (T)0;
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                if (p.op == PMX_PROX_UNITY_PLUS) v[c] = v[c] < 0.f ? 0.f : v[c];
-                s += ok[c] ? v[c] : 0.f;
+                if (p.op == PMX_PROX_UNITY_PLUS) v[c] = v[c] < (T)0 ? (T)0 : v[c];
+                s += ok[c] ? v[c] : (T)0;
             }
-            s = row_sum32(s);
+            s = row_sum<T, G>(s);
 #pragma unroll
             for (int c = 0; c < NC; ++c) v[c] = v[c] / s;
             break;
@@ -224,21 +239,21 @@ __device__ __forceinline__ void prox_one(float (&v)[NC], const bool (&ok)[NC], c
         default: {
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                const float th = (float)p.thresh;                           // (fp32 arithmetic: the threshold as the fp32 value it always was)
-                const float t = p.relative ? th * sk[c] : th;               // operators.py:4-14
-                float x = v[c];
+                const T th = (T)p.thresh;                                   // (float: the threshold as the fp32 value it always was; double: as it is)
+                const T t = p.relative ? th * sk[c] : th;                   // operators.py:4-14
+                T x = v[c];
                 switch (p.op) {
-                    case PMX_PROX_MIN: x = (x - t < 0.f) ? t : x; break;             // operators.py:66-68
-                    case PMX_PROX_MAX: x = (x - t > 0.f) ? t : x; break;             // operators.py:82-84
-                    case PMX_PROX_HARD: x = (fabsf(x) < t) ? 0.f : x; break;         // operators.py:125-127
-                    case PMX_PROX_HARD_PLUS: x = (fabsf(x) < t) ? 0.f : x; x = x < 0.f ? 0.f : x; break;
+                    case PMX_PROX_MIN: x = (x - t < (T)0) ? t : x; break;            // operators.py:66-68
+                    case PMX_PROX_MAX: x = (x - t > (T)0) ? t : x; break;            // operators.py:82-84
+                    case PMX_PROX_HARD: x = (fabs(x) < t) ? (T)0 : x; break;         // operators.py:125-127
+                    case PMX_PROX_HARD_PLUS: x = (fabs(x) < t) ? (T)0 : x; x = x < (T)0 ? (T)0 : x; break;
                     case PMX_PROX_SOFT:
                     case PMX_PROX_SOFT_PLUS: {                                       // sign(X) * plus(|X| - t)
-                        float m = fabsf(x) - t;
-                        m = m < 0.f ? 0.f : m;
-                        const float sg = (float)(x > 0.f) - (float)(x < 0.f);
+                        T m = fabs(x) - t;
+                        m = m < (T)0 ? (T)0 : m;
+                        const T sg = (T)(x > (T)0) - (T)(x < (T)0);
                         x = sg * m;
-                        if (p.op == PMX_PROX_SOFT_PLUS) x = x < 0.f ? 0.f : x;
+                        if (p.op == PMX_PROX_SOFT_PLUS) x = x < (T)0 ? (T)0 : x;
                         break;
                     }
                     default: break;
@@ -249,10 +264,10 @@ __device__ __forceinline__ void prox_one(float (&v)[NC], const bool (&ok)[NC], c
     }
 }
 
-template <int NC>
-__device__ __forceinline__ void prox_row(float (&v)[NC], const bool (&ok)[NC], const ProxSeq& ps, const float (&sk)[NC]) {
+template <class T, int NC, int G = 32>
+__device__ __forceinline__ void prox_row(T (&v)[NC], const bool (&ok)[NC], const ProxSeq& ps, const T (&sk)[NC]) {
     for (int r = 0; r < ps.repeat; ++r)
-        for (int q = 0; q < ps.n; ++q) prox_one<NC>(v, ok, ps.seq[q], sk);
+        for (int q = 0; q < ps.n; ++q) prox_one<T, NC, G>(v, ok, ps.seq[q], sk);
 }
 
 // row iteration: half-wave h of the grid handles rows h, h + H, h + 2H, ...
@@ -392,7 +407,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_prox_apply(ProxArgs a) {
             v[c] = ok[c] ? a.X[r * K + kk] : 0.f;
             sk[c] = ok[c] ? a.stepk[kk] : 0.f;
         }
-        prox_row<NC>(v, ok, a.prox, sk);
+        prox_row(v, ok, a.prox, sk);
 #pragma unroll
         for (int c = 0; c < NC; ++c)
             if (ok[c]) a.X[r * K + l32 + 32 * c] = v[c];
@@ -484,7 +499,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_pgm_update(PgmArgs a) {
                 if (ok[c]) a.T[j][r * K + l32 + 32 * c] = v[c];
             continue;
         }
-        if (mode == 0) prox_row<NC>(v, ok, px, sk);
+        if (mode == 0) prox_row(v, ok, px, sk);
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             if (ok[c]) {
@@ -616,7 +631,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_bt_update(BtArgs a) {
                 }
             continue;
         }
-        if (a.mode[j] == 0) prox_row<NC>(v, ok, a.prox[j], sk);
+        if (a.mode[j] == 0) prox_row(v, ok, a.prox[j], sk);
 #pragma unroll
         for (int c = 0; c < NC; ++c)
             if (ok[c]) {
@@ -1088,7 +1103,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_pgm_unity(PgmUnityArgs aa) {
             if (ub.div && ok[c]) v[c] = v[c] / tot[l32 + 32 * c];
             sk[c] = s;
         }
-        for (int p = ub.p0; p < ub.p1; ++p) prox_one<NC>(v, ok, px.seq[p % px.n], sk);
+        for (int p = ub.p0; p < ub.p1; ++p) prox_one(v, ok, px.seq[p % px.n], sk);
         if (!finish) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
@@ -1432,7 +1447,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_ada_sub(SubArgs a) {
             float v[NC];
 #pragma unroll
             for (int c = 0; c < NC; ++c) v[c] = z[c] - rat[c] * ps[c] * (z[c] - x[c]);
-            prox_row<NC>(v, ok, a.prox[j], gam);
+            prox_row(v, ok, a.prox[j], gam);
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 if (ok[c]) {
@@ -1530,7 +1545,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_ada_finish(FinishArgs a) {
                 float v[NC];
 #pragma unroll
                 for (int c = 0; c < NC; ++c) v[c] = z[c] - rat[c] * ps[c] * (z[c] - x[c]);
-                prox_row<NC>(v, ok, a.s.prox[j], gam);
+                prox_row(v, ok, a.s.prox[j], gam);
 #pragma unroll
                 for (int c = 0; c < NC; ++c) z[c] = v[c];
             }
@@ -1887,7 +1902,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_ada_tail(TailArgs a) {
                     float v[NC];
 #pragma unroll
                     for (int c = 0; c < NC; ++c) v[c] = z[c] - rat[c] * ps[c] * (z[c] - x[c]);
-                    prox_row<NC>(v, ok, a.prox[j], gam);
+                    prox_row(v, ok, a.prox[j], gam);
 #pragma unroll
                     for (int c = 0; c < NC; ++c) {
                         if (SUMS && ok[c]) {
@@ -2231,7 +2246,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_bsdmm_update(BsdmmArgs a) {
                     if (ok[c]) a.Tf[r * K + l32 + 32 * c] = v[c];
                 continue;
             }
-            if (!(a.stage == 2 && a.host_f)) prox_row<NC>(v, ok, a.prox_f, sk);
+            if (!(a.stage == 2 && a.host_f)) prox_row(v, ok, a.prox_f, sk);
 #pragma unroll
             for (int c = 0; c < NC; ++c)
                 if (ok[c]) {
@@ -2266,7 +2281,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_bsdmm_update(BsdmmArgs a) {
                 zn[c] = hosted ? (ok[c] ? a.T[i][e] : 0.f) : v[c] + uo[c];
                 sgk[c] = sg;
             }
-            if (!hosted) prox_row<NC>(zn, ok, a.prox_g[i], sgk);
+            if (!hosted) prox_row(zn, ok, a.prox_g[i], sgk);
 #pragma unroll
             for (int c = 0; c < NC; ++c)
                 if (ok[c]) {

@@ -1602,8 +1602,7 @@ static int pgm64_enqueue_iteration(pmx_ctx* c) {
     u.omega_next = next_omega64(c);
     const int64_t rmax = c->rows[0] > c->rows[1] ? c->rows[0] : c->rows[1];
     const int nbx = (int)((rmax + EW_THREADS / 32 - 1) / (EW_THREADS / 32));      // <= 256: M, N <= 8192
-    if (c->f64big) launch_pgm64b_update(u, c->stream);
-    else launch_pgm64_update(u, nbx, c->stream);                                   // algorithms.py:107-108
+    launch_pgm64b_update(u, c->f64big ? EW_BLOCKS : nbx, c->stream);               // algorithms.py:107-108
     enqueue_pgm_decide(c);                                                         // algorithms.py:130-135
     HIP_CHECK(hipGetLastError());
     c->it += 1;
@@ -1636,7 +1635,7 @@ static int pgm64_bt_iteration(pmx_ctx* c) {
     if (rc != PMX_OK) return rc;
     Fold64Args f{};
     for (int j = 0; j < 2; ++j) { f.slab[j] = c->slabd[j]; f.nslab[j] = j == 0 ? c->nSlabA : c->nSlabS; f.G[j] = c->Gd[j]; f.count[j] = c->rows[j] * c->K; }
-    launch_fold64b(f, c->stream);
+    launch_fold64b(f, 1024, c->stream);
     Bt64Args u{};
     for (int j = 0; j < 2; ++j) {
         u.X[j] = c->Xd[j]; u.E[j] = c->Xed[j]; u.Xp[j] = c->Xprevd[j]; u.G[j] = c->Gd[j];
@@ -1706,8 +1705,7 @@ extern "C" int pmx_grad(pmx_ctx* c) {
         if (rc != PMX_OK) return rc;
         Fold64Args f{};
         for (int j = 0; j < 2; ++j) { f.slab[j] = c->slabd[j]; f.nslab[j] = j == 0 ? c->nSlabA : c->nSlabS; f.G[j] = c->Gd[j]; f.count[j] = c->rows[j] * c->K; }
-        if (c->f64big) launch_fold64b(f, c->stream);
-        else launch_fold64(f, c->stream);
+        launch_fold64b(f, c->f64big ? 1024 : 64, c->stream);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(c->stream));
         return PMX_OK;

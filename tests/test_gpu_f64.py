@@ -273,8 +273,9 @@ def test_fp64_bsdmm_constraint_variables_and_convergence(pm, orc):
 
 
 def test_fp64_operators_and_convergence(pm, orc):
-    """every device operator in fp64 inside pgm (unity along the short axis, soft threshold, alternating projections) and a run
-    that converges: iteration count and flags equal to the oracle's, factors to 1e-10"""
+    """device operators in fp64 inside pgm (unity_plus along the short axis, a relative soft and an absolute hard threshold) and a
+    run that converges: iteration count and flags equal to the oracle's, factors to 1e-10.  Every op-code, on every instantiation
+    of the fp64 kernels: tests/test_gpu_f64_operators.py"""
     from functools import partial
     ops = pm.operators
     Y, A0, S0 = orc.synthetic_problem(150, 333, 6, np.float64, unity_S=True, seed=9)
