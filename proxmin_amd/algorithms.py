@@ -28,7 +28,7 @@ from functools import partial
 import numpy as np
 
 from . import _lib, operators, utils
-from .engine import DeviceNMF, open_weighted, as_device_array, DeviceArrayRef
+from .engine import DeviceNMF, open_weighted, as_device_array, DeviceArrayRef, f64_applies
 
 logger = logging.getLogger("proxmin")
 
@@ -61,9 +61,14 @@ def _problem_from_grad(X, grad):
     return Y, A, S, _nmf._weights(kw.get("W", 1), Y.shape)
 
 
-def _host_gradient(dev, grad, dt, accelerated_eval=True):
+def _host_pair(dev, buf, dt):
+    """Both blocks of a two-block device buffer (the evaluation point, the gradient) on the host, in the caller's dtype."""
+    return dev.get(buf, 0).astype(dt), np.ascontiguousarray(dev.get(buf, 1)).astype(dt)
+
+
+def _host_gradient(dev, grad, dt):
     """Evaluate a user `grad` at the device's current evaluation point and hand the result to the device."""
-    Xe = (dev.get(_lib.BUF_EVAL_A, 0).astype(dt), np.ascontiguousarray(dev.get(_lib.BUF_EVAL_A, 1)).astype(dt))
+    Xe = _host_pair(dev, _lib.BUF_EVAL_A, dt)
     G = utils._as_tuple(grad(*Xe))
     assert len(G) == 2 and np.shape(G[0]) == Xe[0].shape and np.shape(G[1]) == Xe[1].shape, "grad must return one array per block"
     dev.put(_lib.BUF_GA, 0, np.asarray(G[0]))
@@ -117,6 +122,13 @@ def _warn_f64_in_f32(Y, A, S):
                        "Pass float32 arrays to silence this." % (A.shape[0], S.shape[1], A.shape[1]))
 
 
+def _f64_call(Y, A, S, W, all_device, weighted):
+    """Does this call take the fp64 kernels?  fp64 arrays on a shape those kernels cover (engine.f64_applies), and nothing of
+    the iteration on the host.  all_device / weighted: the solver's own "nothing needs the host" and the kernel family asked for."""
+    return bool(all_device and Y is not None and not isinstance(W, DeviceArrayRef) and all(x.dtype == np.float64 for x in (Y, A, S))
+                and f64_applies(A.shape[0], S.shape[1], A.shape[1], weighted=weighted))
+
+
 def _prox_pair(prox, n=2):
     prox = utils._as_tuple(prox)
     if len(prox) == 1:
@@ -142,6 +154,28 @@ def _wants_iterates(callback):
     return callback is not None and not isinstance(callback, utils.NullCallback)
 
 
+def _iterate(dev, A, S, max_iter, callback, advance, stop_iteration=True):
+    """The host loop of every route that is not one fused call: the callback on the pre-update iterate (algorithms.py:90,
+    :368, :802), ONE iteration through `advance(it) -> Result`, the factors written back, stop when the device says so.
+    A StopIteration from the callback ends pgm and adaprox quietly; bsdmm has no handler (stop_iteration=False) and its
+    caller gets the exception itself -- which is why this is a plain function: a generator would hand it on as
+    RuntimeError (PEP 479).  -> the last Result (None: no iteration ran)."""
+    res = None
+    for it in range(max_iter):
+        if _wants_iterates(callback):
+            try:
+                callback(A, S, it=it)
+            except StopIteration:
+                if stop_iteration:
+                    break
+                raise
+        res = advance(it)
+        _write_back(dev, A, S)
+        if res.stopped:
+            break
+    return res
+
+
 _warned = set()
 
 
@@ -153,38 +187,42 @@ def _warn_host_path(what):
                        "the whole iteration on the GPU" % what)
 
 
-def _warn_long_axis(j, exc):
-    if "unity-long-%d" % j not in _warned:
-        _warned.add("unity-long-%d" % j)
+def _warn_long_axis(j, exc, key="unity-long-%d"):
+    if key % j not in _warned:
+        _warned.add(key % j)
         logger.warning("proxmin_amd: %s: one iteration per call, its argument goes through the host" % exc)
 
 
+def _seq_or_host(q, j, what, fill=operators.prox_id, long_key="unity-long-%d", long_axis=None):
+    """One operator of block j -> (its device sequence, None) for an operator of this library, (the sequence of `fill` for its
+    device slot, q) for anything else: a user callable, with the host-path warning, or this library's prox_unity* along the
+    block's LONG axis (operators.NotFusable: its grid-wide sum is a stand-alone device kernel, so it takes the path between
+    launches that a user callable takes -- calling it on the host copy runs that kernel; no host arithmetic), with the
+    long-axis warning under `long_key`.  long_axis: a list (pgm) whose entry j then receives (the sequence with its
+    long-axis entries, the NotFusable) INSTEAD of the warning, which is left to _fuse_long_axis."""
+    try:
+        return operators.device_proxseq(q, j, for_solver=True), None
+    except NotImplementedError as exc:
+        if not callable(q):
+            raise
+        if not isinstance(exc, operators.NotFusable):
+            _warn_host_path("%s of block %d (%r)" % (what, j, q))
+        elif long_axis is not None:
+            long_axis[j] = (operators.device_proxseq(q, j, for_solver="pgm"), exc)
+        else:
+            _warn_long_axis(j, exc, long_key)
+        return operators.device_proxseq(fill, j), q
+
+
 def _split_prox(prox, none_is_id, long_axis=None):
-    """-> (device operator sequences, [callable or None per block]): operators of this library become device sequences,
-    anything else is kept for the host round trip (its device slot is prox_id / no operator).  long_axis: a list (pgm) that
-    receives, per block, None or (sequence with its long-axis prox_unity* entries, the NotFusable raised for it); the
-    warning for such a block is then left to the caller, who may still keep the sequence on the device (_fuse_long_axis)."""
-    seqs, host = [], []
-    for j, p in enumerate(prox):
-        q = operators.prox_id if (p is None and none_is_id) else p
-        if long_axis is not None:
-            long_axis.append(None)
-        try:
-            seqs.append(operators.device_proxseq(q, j, for_solver=True))
-            host.append(None)
-        except NotImplementedError as exc:
-            if not callable(q):
-                raise
-            if isinstance(exc, operators.NotFusable):
-                if long_axis is not None:
-                    long_axis[j] = (operators.device_proxseq(q, j, for_solver="pgm"), exc)
-                else:
-                    _warn_long_axis(j, exc)
-            else:
-                _warn_host_path("prox of block %d (%r)" % (j, q))
-            seqs.append(operators.device_proxseq(operators.prox_id if none_is_id else None, j))
-            host.append(q)
-    return seqs, host
+    """-> (device operator sequences, [callable or None per block]) of pgm's and adaprox's `prox` (_seq_or_host per block;
+    prox=None is prox_id in pgm and no operator at all in adaprox).  long_axis: a list (pgm) that receives, per block, None
+    or the entry that lets the caller keep a long-axis sequence on the device after all (_fuse_long_axis)."""
+    fill = operators.prox_id if none_is_id else None
+    if long_axis is not None:
+        long_axis.extend([None] * len(prox))
+    pairs = [_seq_or_host(fill if p is None else p, j, "prox", fill, long_axis=long_axis) for j, p in enumerate(prox)]
+    return [sq for sq, _ in pairs], [h for _, h in pairs]
 
 
 def _fuse_long_axis(seqs, host_prox, long_axis, host_route):
@@ -228,6 +266,29 @@ def _user_steps(s, what, shapes):
             arrs.append(a)
             orig.append(v)
     return tuple(scal), arrs, orig
+
+
+class _UserStep:
+    """pgm's protocol for a user `step`: the reference's signature probe once (algorithms.py:73-77: does the callable take
+    `grads`?), then one call per iteration at the device's evaluation point with the arguments the reference passes."""
+
+    def __init__(self, step, A, S):
+        self.step, self.shapes = step, (A.shape, S.shape)
+        try:
+            step(A, S, it=0, grads=(A, S))
+            self.takes_grads = True
+        except TypeError:
+            self.takes_grads = False
+
+    def __call__(self, dev, it, dt):
+        """-> _user_steps() of what the callable returns.  takes_grads: the device's gradient buffers must hold the gradient
+        at the evaluation point (pmx_pgm_split phase 0) -- the caller's business, the routes differ in it."""
+        Xe = _host_pair(dev, _lib.BUF_EVAL_A, dt)
+        if self.takes_grads:
+            ret = self.step(*Xe, it=it, grads=_host_pair(dev, _lib.BUF_GA, dt))
+        else:
+            ret = self.step(*Xe, it=it)
+        return _user_steps(ret, "step", self.shapes)
 
 
 def _component_steps(alpha, K, j):
@@ -308,45 +369,46 @@ def pgm(X, grad, step, prox=None, accelerated=False, backtracking=False, f=None,
     # (scaled_step_pgm stands for `lambda *X, it=None: tuple(c * s for s in step_pgm(*X))`: step_pgm with ITS default W = 1 -- the
     # unweighted Lipschitz rule -- also when the likelihood carries weights)
     # [r4] fp64 inputs of a small problem, everything of the iteration on the device: fp64 arithmetic (PMX_MODE_F64)
-    from .engine import f64_applies
     # [r6] ... at any size up to K = 128, weighted or not, with the Beck-Teboulle line search (the matrix-core kernels: k_big_f64.hip)
-    f64 = (not slow and not fused_long and bb is None and Y is not None and not isinstance(W, DeviceArrayRef)
-           and all(x.dtype == np.float64 for x in (Y, A, S)) and f64_applies(A.shape[0], S.shape[1], A.shape[1], weighted=W is not None or backtracking))
+    f64 = _f64_call(Y, A, S, W, all_device=not slow and not fused_long and bb is None, weighted=W is not None or backtracking)
+    any_host_prox = any(h is not None for h in host_prox)
     with _open_device(Y, A, S, W, f64=f64, f64_mfma=backtracking) as dev:
         dev.pgm_begin(seqs, accelerated=accelerated, step_scale=scale, fixed_steps=(1.0, 1.0) if user_step is not None else fixed,
                       e_rel=e_rel, bb=(bb.type, bb.r) if bb is not None else None, backtracking=backtracking,
                       host_prox=[h is not None for h in host_prox], unweighted_rule=W is not None and user_step is None and fixed is None and bb is None)
-        res = None
-        it_done = 0
         dt = A.dtype
-        steps_user, step_arrays = None, [None, None]
-        if bt_user_prox:
-            takes_grads = False
-            if user_step is not None:                            # the reference's signature probe (algorithms.py:73-77)
-                try:
-                    user_step(A, S, it=0, grads=(A, S))
-                    takes_grads = True
-                except TypeError:
-                    takes_grads = False
-            for it in range(max_iter):
-                if _wants_iterates(callback):
-                    try:
-                        callback(A, S, it=it)
-                    except StopIteration:
-                        break
-                if user_step is not None:
-                    if takes_grads:
-                        dev.pgm_split(0)                         # the gradient at the evaluation point, for the callable only
-                    Xe = (dev.get(_lib.BUF_EVAL_A, 0).astype(dt), np.ascontiguousarray(dev.get(_lib.BUF_EVAL_A, 1)).astype(dt))
-                    if takes_grads:
-                        Gh = (dev.get(_lib.BUF_GA, 0).astype(dt), np.ascontiguousarray(dev.get(_lib.BUF_GA, 1)).astype(dt))
-                        ret = user_step(*Xe, it=it, grads=Gh)
-                    else:
-                        ret = user_step(*Xe, it=it)
-                    steps, step_arrays, _ = _user_steps(ret, "step", (A.shape, S.shape))
+        ustep = _UserStep(user_step, A, S) if user_step is not None else None
+        # what the user's step returned last (kept ACROSS iterations: the returned steps are the last iteration's), and whether
+        # the device still holds step arrays of an earlier iteration
+        steps_user, step_arrays, arrays_on = None, [None, None], False
+
+        def advance(it):
+            """One iteration in pieces (algorithms.py:87-135): the gradient at the (extrapolated) point on the device or from
+            the user's `grad`, the user's step / prox on the host with exactly the arguments the reference passes, the update,
+            extrapolation and stopping test on the device again."""
+            nonlocal steps_user, step_arrays, arrays_on
+            if user_grad:                                       # grads = grad(*_X) (algorithms.py:105); never with the line search
+                _host_gradient(dev, grad, dt)
+            r0 = steps = None
+            if not backtracking:
+                r0 = dev.pgm_split(0)
+            elif ustep is not None and ustep.takes_grads:
+                dev.pgm_split(0)                                # the gradient at the evaluation point, for the callable only
+            if ustep is not None:
+                # scalars per block, or arrays that broadcast against the blocks (uploaded element by element)
+                steps, step_arrays, steps_user = ustep(dev, it, dt)
+                if backtracking:
+                    # algorithms.py:105-127 with a Python `step`: its scalars become the constants of ONE device iteration with
+                    # the line search (T[j] S[j] in the reference: T lives on the device, S comes from here)
                     if any(a is not None for a in step_arrays):
                         raise NotImplementedError("array-valued steps from a user `step` together with backtracking are not implemented")
                     dev.pgm_set_fixed_steps(steps)
+                elif any(a is not None for a in step_arrays) or arrays_on:
+                    dev.pgm_step_arrays(step_arrays)
+                    arrays_on = any(a is not None for a in step_arrays)
+            if backtracking and not any_host_prox:              # the Beck-Teboulle loop on the device
+                return dev.pgm_run(1)
+            if backtracking:
                 need, eff, res = dev.pgm_bt_split(0)
                 while need:                                      # prox[j](_X[j] - T[j] S[j] G[j], T[j] S[j]) (algorithms.py:108, :125)
                     for j in range(2):
@@ -354,114 +416,32 @@ def pgm(X, grad, step, prox=None, accelerated=False, backtracking=False, f=None,
                             T = np.ascontiguousarray(dev.get(_lib.BUF_BT_A, j)).astype(dt)
                             dev.put(_lib.BUF_BT_A, j, np.asarray(host_prox[j](T, dt.type(eff[j]))))
                     need, eff, res = dev.pgm_bt_split(1)
-                _write_back(dev, A, S)
-                it_done = res.total_iterations
-                if res.stopped:
-                    break
-        elif bt_user_step:
-            # algorithms.py:105-127 with a Python `step`: its scalars become the constants of ONE device iteration with the
-            # line search (T[j] S[j] in the reference: T lives on the device, S comes from here)
-            takes_grads = False
-            try:                                                # the reference's signature probe (algorithms.py:73-77)
-                user_step(A, S, it=0, grads=(A, S))
-                takes_grads = True
-            except TypeError:
-                takes_grads = False
-            for it in range(max_iter):
-                if _wants_iterates(callback):
-                    try:
-                        callback(A, S, it=it)
-                    except StopIteration:
-                        break
-                if takes_grads:
-                    dev.pgm_split(0)                            # the gradient at the evaluation point, for the callable only
-                Xe = (dev.get(_lib.BUF_EVAL_A, 0).astype(dt), np.ascontiguousarray(dev.get(_lib.BUF_EVAL_A, 1)).astype(dt))
-                if takes_grads:
-                    Gh = (dev.get(_lib.BUF_GA, 0).astype(dt), np.ascontiguousarray(dev.get(_lib.BUF_GA, 1)).astype(dt))
-                    ret = user_step(*Xe, it=it, grads=Gh)
-                else:
-                    ret = user_step(*Xe, it=it)
-                steps, step_arrays, _ = _user_steps(ret, "step", (A.shape, S.shape))
-                if any(a is not None for a in step_arrays):
-                    raise NotImplementedError("array-valued steps from a user `step` together with backtracking are not implemented")
-                dev.pgm_set_fixed_steps(steps)
-                res = dev.pgm_run(1)
-                _write_back(dev, A, S)
-                it_done = res.total_iterations
-                if res.stopped:
-                    break
-        elif slow:
-            # One iteration per pass, in pieces (algorithms.py:87-135): the gradient at the (extrapolated) point on the
-            # device, the user's step / prox on the host with exactly the arguments the reference passes, the update,
-            # extrapolation and stopping test on the device again.
-            takes_grads = False
-            arrays_on, steps_user, step_arrays = False, None, [None, None]
-            if user_step is not None:                           # the reference's signature probe (algorithms.py:73-77)
-                try:
-                    user_step(A, S, it=0, grads=(A, S))
-                    takes_grads = True
-                except TypeError:
-                    takes_grads = False
-            for it in range(max_iter):
-                if _wants_iterates(callback):
-                    try:
-                        callback(A, S, it=it)
-                    except StopIteration:
-                        break
-                if user_grad:                                   # grads = grad(*_X) (algorithms.py:105)
-                    _host_gradient(dev, grad, dt)
-                r0 = dev.pgm_split(0)
-                steps = None
-                if user_step is not None:
-                    Xe = (dev.get(_lib.BUF_EVAL_A, 0).astype(dt), np.ascontiguousarray(dev.get(_lib.BUF_EVAL_A, 1)).astype(dt))
-                    if takes_grads:
-                        Gh = (dev.get(_lib.BUF_GA, 0).astype(dt), np.ascontiguousarray(dev.get(_lib.BUF_GA, 1)).astype(dt))
-                        ret = user_step(*Xe, it=it, grads=Gh)
+                return res
+            if any_host_prox:
+                dev.pgm_split(1, steps)
+                for j, h in enumerate(host_prox):
+                    if h is None:
+                        continue
+                    T = np.ascontiguousarray(dev.get(_lib.BUF_TMP_A, j)).astype(dt)
+                    if steps is not None and step_arrays[j] is not None:
+                        sj = np.asarray(steps_user[j]).astype(dt)        # the array, as the reference hands it on
                     else:
-                        ret = user_step(*Xe, it=it)
-                    # scalars per block, or arrays that broadcast against the blocks (uploaded element by element)
-                    steps, step_arrays, steps_user = _user_steps(ret, "step", (A.shape, S.shape))
-                    if any(a is not None for a in step_arrays) or arrays_on:
-                        dev.pgm_step_arrays(step_arrays)
-                        arrays_on = any(a is not None for a in step_arrays)
-                if any(h is not None for h in host_prox):
-                    dev.pgm_split(1, steps)
-                    for j, h in enumerate(host_prox):
-                        if h is None:
-                            continue
-                        T = np.ascontiguousarray(dev.get(_lib.BUF_TMP_A, j)).astype(dt)
-                        if steps is not None and step_arrays[j] is not None:
-                            sj = np.asarray(steps_user[j]).astype(dt)        # the array, as the reference hands it on
-                        else:
-                            sj = dt.type(steps[j] if steps is not None else r0.steps[j])
-                        out = h(T, sj)                           # prox(X, step) -> X' (algorithms.py:37-39, :108)
-                        dev.put(_lib.BUF_TMP_A, j, np.asarray(out))
-                res = dev.pgm_split(2, steps)
-                _write_back(dev, A, S)
-                it_done = res.total_iterations
-                if res.stopped:
-                    break
-        elif _wants_iterates(callback):
-            for it in range(max_iter):
-                try:
-                    callback(A, S, it=it)                       # algorithms.py:90 (pre-update iterate)
-                except StopIteration:
-                    break
-                res = dev.pgm_run(1)
-                _write_back(dev, A, S)
-                it_done = res.total_iterations
-                if res.stopped:
-                    break
+                        sj = dt.type(steps[j] if steps is not None else r0.steps[j])
+                    out = h(T, sj)                               # prox(X, step) -> X' (algorithms.py:37-39, :108)
+                    dev.put(_lib.BUF_TMP_A, j, np.asarray(out))
+            return dev.pgm_split(2, steps)
+
+        if slow or _wants_iterates(callback):
+            res = _iterate(dev, A, S, max_iter, callback, advance if slow else lambda it: dev.pgm_run(1))
         else:
             res = dev.pgm_run(max_iter)
-            it_done = res.total_iterations
             _write_back(dev, A, S)
-        G = (dev.get(_lib.BUF_GA, 0).astype(dt), np.ascontiguousarray(dev.get(_lib.BUF_GA, 1)).astype(dt))
+        G = _host_pair(dev, _lib.BUF_GA, dt)
     converged = tuple(bool(c) for c in res.converged) if res is not None else (False, False)
     steps = (dt.type(res.steps[0]), dt.type(res.steps[1])) if res is not None else (None, None)
-    if res is not None and slow and user_step is not None and steps_user is not None:
+    if res is not None and steps_user is not None:
         steps = tuple(steps_user[j] if step_arrays[j] is not None else steps[j] for j in range(2))   # arrays go back as returned
-    logger.info("Completed {0} iterations".format(it_done))
+    logger.info("Completed {0} iterations".format(res.total_iterations if res is not None else 0))
     if not all(converged):
         logger.warning("Solution did not converge")
     return converged, G, steps
@@ -512,9 +492,10 @@ def adaprox(X, grad, step, prox=None, scheme="adam", b1=0.9, b2=0.999, eps=1e-8,
         assert len(Vhat) == 2 and all(vh.shape == x.shape for x, vh in zip(Xs, Vhat))
 
     # [r4] fp64 inputs of a small problem: fp64 arithmetic on the device (k_small_f64.hip: k64_ada_iter), as the reference's own
-    from .engine import f64_applies
-    f64 = (not slow and Y is not None and not isinstance(W, DeviceArrayRef) and all(x.dtype == np.float64 for x in (Y, A, S))
-           and f64_applies(A.shape[0], S.shape[1], A.shape[1], weighted=W is not None))
+    f64 = _f64_call(Y, A, S, W, all_device=not slow, weighted=W is not None)
+    any_host_prox = any(h is not None for h in host_prox)
+    dt = A.dtype
+    K = A.shape[1]
     with _open_device(Y, A, S, W, f64=f64) as dev:
         for j in range(2):
             if warm:
@@ -526,84 +507,57 @@ def adaprox(X, grad, step, prox=None, scheme="adam", b1=0.9, b2=0.999, eps=1e-8,
                           prox_max_iter=prox_max_iter, warm_moments=warm, warm_vhat=Vhat is not None,
                           fixed_alpha=fixed, e_rel=e_rel, host_step=user_step is not None,
                           host_prox=[h is not None for h in host_prox])
-        res = None
-        it_done = 0
-        host_sub = [0, 0]
-        if max_iter > 0 and slow:
-            # One iteration per pass (algorithms.py:365-410): user step -> device moments and update -> the proximal loop
-            # of a block with a user-defined prox around that callable on the host (:383-400, with the reference's own
-            # expressions) -> the other block's loop, X <- z, stopping test and next step sizes on the device.
-            dt = A.dtype
-            K = A.shape[1]
-            for it in range(max_iter):
-                if _wants_iterates(callback):
-                    try:
-                        callback(A, S, it=it)
-                    except StopIteration:
-                        break
-                alpha = None
-                if user_grad:                                                      # G = grad(*X) (algorithms.py:369)
-                    _host_gradient(dev, grad, dt)
-                if user_step is not None:
-                    alpha = utils._as_tuple(user_step(A, S, it=it))                  # algorithms.py:370
-                    assert len(alpha) == 2, "step must return one Alpha per block"
-                    dev.adaprox_set_alpha(_component_steps(alpha[0], K, 0), _component_steps(alpha[1], K, 1))
-                elif fixed is not None:
-                    # nmf.constant_step: the device keeps the two constants (adaprox_begin(fixed_alpha=...)); recomputing the
-                    # default rule here would overwrite DevStatus::alpha with mean(X)/10 (and clear the halt flag mid-run)
-                    alpha = (dt.type(fixed[0]), dt.type(fixed[1]))
-                elif any(h is not None for h in host_prox):
-                    aA, aS = dev.step_adaprox()                                    # the rule the device applies (nmf.py:93)
-                    alpha = (aA.astype(dt), aS.astype(dt)[:, None])
-                if not any(h is not None for h in host_prox):                      # only the step rule is the user's
-                    res = dev.adaprox_run(b1[it:it + 1], b1[it - 1])
-                    _write_back(dev, A, S)
-                    it_done = res.total_iterations
-                    if res.stopped:
-                        break
+
+        def run_one(it):
+            return dev.adaprox_run(b1[it:it + 1], b1[it - 1])   # b1[-1] at it = 0, like algorithms.py:213
+
+        def advance(it):
+            """One iteration in pieces (algorithms.py:365-410): user grad / step -> device moments and update -> the proximal
+            loop of a block with a user-defined prox around that callable on the host (:383-400, with the reference's own
+            expressions) -> the other block's loop, X <- z, stopping test and next step sizes on the device."""
+            alpha = None
+            if user_grad:                                                      # G = grad(*X) (algorithms.py:369)
+                _host_gradient(dev, grad, dt)
+            if user_step is not None:
+                alpha = utils._as_tuple(user_step(A, S, it=it))                  # algorithms.py:370
+                assert len(alpha) == 2, "step must return one Alpha per block"
+                dev.adaprox_set_alpha(_component_steps(alpha[0], K, 0), _component_steps(alpha[1], K, 1))
+            elif fixed is not None:
+                # nmf.constant_step: the device keeps the two constants (adaprox_begin(fixed_alpha=...)); recomputing the
+                # default rule here would overwrite DevStatus::alpha with mean(X)/10 (and clear the halt flag mid-run)
+                alpha = (dt.type(fixed[0]), dt.type(fixed[1]))
+            elif any_host_prox:
+                aA, aS = dev.step_adaprox()                                    # the rule the device applies (nmf.py:93)
+                alpha = (aA.astype(dt), aS.astype(dt)[:, None])
+            if not any_host_prox:                                              # only the gradient / step rule is the user's
+                return run_one(it)
+            _, maxpsi = dev.adaprox_split(0, it, b1[it], b1[it - 1])
+            taus = [0, 0]
+            for j, h in enumerate(host_prox):
+                if h is None:
                     continue
-                _, maxpsi = dev.adaprox_split(0, it, b1[it], b1[it - 1])
-                taus = [0, 0]
-                for j, h in enumerate(host_prox):
-                    if h is None:
-                        continue
-                    Xj = np.ascontiguousarray(dev.get(_lib.BUF_A, j)).astype(dt)
-                    Psi = np.ascontiguousarray(dev.get(_lib.BUF_PSI_A, j)).astype(dt)
-                    Alpha = alpha[j] if not np.isscalar(alpha[j]) else dt.type(alpha[j])
-                    z = Xj.copy()
-                    gamma = Alpha / dt.type(maxpsi[j])                              # algorithms.py:384
-                    tau = 0
-                    for tau in range(1, prox_max_iter + 1):                        # :386-393
-                        z_ = h(z - gamma / Alpha * Psi * (z - Xj), gamma)
-                        converged_ = utils.l2sq(z_ - z) <= e_rel[j] ** 2 * utils.l2sq(z)
-                        z = z_
-                        if converged_:
-                            break
-                    dev.put(_lib.BUF_A, j, z)                                      # X[j][:] = z (:400)
-                    taus[j] = tau
-                    host_sub[j] += tau
-                res, _ = dev.adaprox_split(1, it, b1[it], b1[it - 1], taus)
-                _write_back(dev, A, S)
-                it_done = res.total_iterations
-                if res.stopped:
-                    break
+                Xj = np.ascontiguousarray(dev.get(_lib.BUF_A, j)).astype(dt)
+                Psi = np.ascontiguousarray(dev.get(_lib.BUF_PSI_A, j)).astype(dt)
+                Alpha = alpha[j] if not np.isscalar(alpha[j]) else dt.type(alpha[j])
+                z = Xj.copy()
+                gamma = Alpha / dt.type(maxpsi[j])                              # algorithms.py:384
+                tau = 0
+                for tau in range(1, prox_max_iter + 1):                        # :386-393
+                    z_ = h(z - gamma / Alpha * Psi * (z - Xj), gamma)
+                    converged_ = utils.l2sq(z_ - z) <= e_rel[j] ** 2 * utils.l2sq(z)
+                    z = z_
+                    if converged_:
+                        break
+                dev.put(_lib.BUF_A, j, z)                                      # X[j][:] = z (:400)
+                taus[j] = tau
+            return dev.adaprox_split(1, it, b1[it], b1[it - 1], taus)[0]
+
+        res = None
+        if slow or _wants_iterates(callback):
+            res = _iterate(dev, A, S, max_iter, callback, advance if slow else run_one)
         elif max_iter > 0:
-            if _wants_iterates(callback):
-                for it in range(max_iter):
-                    try:
-                        callback(A, S, it=it)                   # algorithms.py:368
-                    except StopIteration:
-                        break
-                    res = dev.adaprox_run(b1[it:it + 1], b1[it - 1])   # b1[-1] at it = 0, like algorithms.py:213
-                    _write_back(dev, A, S)
-                    it_done = res.total_iterations
-                    if res.stopped:
-                        break
-            else:
-                res = dev.adaprox_run(b1, b1[-1])
-                it_done = res.total_iterations
-                _write_back(dev, A, S)
-        dt = A.dtype
+            res = dev.adaprox_run(b1, b1[-1])
+            _write_back(dev, A, S)
         outM = tuple(np.ascontiguousarray(dev.get(_lib.BUF_MA, j)).astype(dt) for j in range(2))
         outV = tuple(np.ascontiguousarray(dev.get(_lib.BUF_VA, j)).astype(dt) for j in range(2))
         if M is not None:
@@ -621,7 +575,7 @@ def adaprox(X, grad, step, prox=None, scheme="adam", b1=0.9, b2=0.999, eps=1e-8,
         else:
             outVhat = [None] * 2
     sub = [int(res.sub_iterations[0]), int(res.sub_iterations[1])] if res is not None else [0, 0]
-    logger.info("Completed {0} iterations and {1} sub-iterations".format(it_done, sub))
+    logger.info("Completed {0} iterations and {1} sub-iterations".format(res.total_iterations if res is not None else 0, sub))
     if check_convergence:
         converged = tuple(bool(c) for c in res.converged) if res is not None else (False, False)
         if not all(converged):
@@ -700,28 +654,12 @@ def _bsdmm_nmf(X, grad, prox, proxs_g=None, steps_g=None, Ls=None, update_order=
             return [None, None]
     er = [e_rel] * N if np.isscalar(e_rel) else list(e_rel)
     ea = [e_abs] * N if np.isscalar(e_abs) else list(e_abs)
-    def _seq_or_host(q, j, what):
-        """device sequence of an operator of this library; (prox_id, callable) for anything else (host round trip)"""
-        q = q if q is not None else operators.prox_id
-        try:
-            return operators.device_proxseq(q, j, for_solver=True), None
-        except NotImplementedError as exc:
-            if not callable(q):
-                raise
-            if isinstance(exc, operators.NotFusable):
-                # [r4] this library's prox_unity* along the block's LONG axis: its grid-wide sum exists as a stand-alone device
-                # kernel only, so the operator takes the same between-launches path a user callable takes (pmx_bsdmm_split) --
-                # calling it on the host copy runs that kernel; no host arithmetic
-                if "unity-long-bsdmm-%d" % j not in _warned:
-                    _warned.add("unity-long-bsdmm-%d" % j)
-                    logger.warning("proxmin_amd: %s: one iteration per call, its argument goes through the host" % exc)
-            else:
-                _warn_host_path("%s of block %d (%r)" % (what, j, q))
-            return operators.device_proxseq(operators.prox_id, j), q
+    def _member(q, j, what):
+        return _seq_or_host(q if q is not None else operators.prox_id, j, what, long_key="unity-long-bsdmm-%d")
 
     seq_f, host_f = [], []
     for j, q in enumerate(prox):
-        sq, h = _seq_or_host(q, j, "prox")
+        sq, h = _member(q, j, "prox")
         seq_f.append(sq)
         host_f.append(h)
     seq_g, host_g = [], []
@@ -733,70 +671,59 @@ def _bsdmm_nmf(X, grad, prox, proxs_g=None, steps_g=None, Ls=None, update_order=
             continue
         if not hasattr(g, "__iter__"):
             g = [g]
-        pairs = [_seq_or_host(q, j, "proxs_g member") for q in g]
+        pairs = [_member(q, j, "proxs_g member") for q in g]
         seq_g.append([sq for sq, _ in pairs])
         host_g.append([h for _, h in pairs])
     slow = any(h is not None for h in host_f) or any(h is not None for hs in host_g for h in hs) or closures is not None
 
     # [r4] fp64 inputs of a small problem: fp64 arithmetic on the device (k_small_f64.hip: k64_bsdmm_block), as the reference's own
-    from .engine import f64_applies
-    f64 = (not slow and Y is not None and all(x.dtype == np.float64 for x in (Y, A, S))
-           and f64_applies(A.shape[0], S.shape[1], A.shape[1]))
+    f64 = _f64_call(Y, A, S, None, all_device=not slow, weighted=False)
     with _open_device(Y, A, S, None, f64=f64) as dev:
         dev.bsdmm_begin(seq_f, seq_g, e_rel=er, e_abs=ea, update_order=order)
-        res = None
         if closures is not None:        # the device's gradient stays zero: X_j - dX comes out of phase 0
             dev.put(_lib.BUF_GA, 0, np.zeros(A.shape, np.float32))
             dev.put(_lib.BUF_GA, 1, np.zeros(S.shape, np.float32))
-        if slow:
-            # One iteration per pass, every block update in pieces (utils.py:307-346): step_f and the gradient on the device,
-            # the user's prox_f on the host, X / dual updates and norms on the device, the user-defined members of proxs_g on
-            # the host with exactly the arguments the reference passes (X + U_i, step_g_i), Boyd's test on the device.
-            dt = A.dtype
-            blocks = order if order is not None else [0, 1]
-            for it in range(max_iter):
-                if _wants_iterates(callback):
-                    callback(A, S, it=it)                       # no StopIteration handler (algorithms.py:802)
-                for o, j in enumerate(blocks):
-                    hf = host_f[j] is not None or closures is not None
-                    mask = sum(1 << i for i, h in enumerate(host_g[j]) if h is not None)
-                    user_sf = float(closures[1]((A, S), j=j)) if closures is not None else 0.0   # steps_f_cb(X, j=j) (algorithms.py:807)
-                    if closures is not None and not user_sf > 0.0:
-                        raise ValueError("steps_f_cb returned %r for block %d: a positive step is required" % (user_sf, j))
-                    r0 = dev.bsdmm_split(j, 0, hf, mask, step_f=user_sf)
-                    step_f = dt.type(r0.steps[j])
-                    rows = A.shape[0] if j == 0 else S.shape[1]
-                    if hf:
-                        T = np.ascontiguousarray(dev.get(_lib.BUF_TMP_A, j)).astype(dt)
-                        if closures is not None:                # proxs_f(X_j - dX, step_f, j=j, Xs=X) (algorithms.py:806, utils.py:338)
-                            out = closures[0](T, step_f, j=j, Xs=(A, S))
-                        else:                                   # prox_j(X - dX - step grad_j, step) (nmf.py:181-185)
-                            out = host_f[j](T, step_f)
-                        dev.put(_lib.BUF_TMP_A, j, np.asarray(out))
-                    dev.bsdmm_split(j, 1, hf, mask)
-                    if mask:
-                        step_g = dt.type(float(r0.steps[j]) * 2.0 * len(host_g[j]))           # utils.get_step_g, identity L (utils.py:269-279)
-                        for i, h in enumerate(host_g[j]):
-                            if h is None:
-                                continue
-                            buf = _lib.BUF_TG0 + j * _lib.MAX_G + i
-                            T = dev._download(buf, rows)
-                            T = np.ascontiguousarray(T if j == 0 else T.T).astype(dt)
-                            out = np.asarray(h(T, step_g))                                   # Z_i = prox_g_i(L X + U_i, step_g_i) (utils.py:295-304)
-                            dev._upload(buf, out if j == 0 else out.T)
-                    res = dev.bsdmm_split(j, 2, hf, mask, last_block=(o == len(blocks) - 1))
-                    if closures is not None:                    # Gauss-Seidel: the next block's closures see this update
-                        _write_back(dev, A, S)
-                _write_back(dev, A, S)
-                if res is not None and res.stopped:
-                    break
-        elif _wants_iterates(callback):
-            for it in range(max_iter):
-                callback(A, S, it=it)                           # no StopIteration handler (algorithms.py:802)
-                res = dev.bsdmm_run(1)
-                _write_back(dev, A, S)
-                if res.stopped:
-                    break
+        dt = A.dtype
+        blocks = order if order is not None else [0, 1]
+
+        def advance(it):
+            """One iteration, every block update in pieces (utils.py:307-346): step_f and the gradient on the device, the
+            user's prox_f on the host, X / dual updates and norms on the device, the user-defined members of proxs_g on the
+            host with exactly the arguments the reference passes (X + U_i, step_g_i), Boyd's test on the device."""
+            for o, j in enumerate(blocks):
+                hf = host_f[j] is not None or closures is not None
+                mask = sum(1 << i for i, h in enumerate(host_g[j]) if h is not None)
+                user_sf = float(closures[1]((A, S), j=j)) if closures is not None else 0.0   # steps_f_cb(X, j=j) (algorithms.py:807)
+                if closures is not None and not user_sf > 0.0:
+                    raise ValueError("steps_f_cb returned %r for block %d: a positive step is required" % (user_sf, j))
+                r0 = dev.bsdmm_split(j, 0, hf, mask, step_f=user_sf)
+                step_f = dt.type(r0.steps[j])
+                rows = A.shape[0] if j == 0 else S.shape[1]
+                if hf:
+                    T = np.ascontiguousarray(dev.get(_lib.BUF_TMP_A, j)).astype(dt)
+                    if closures is not None:                # proxs_f(X_j - dX, step_f, j=j, Xs=X) (algorithms.py:806, utils.py:338)
+                        out = closures[0](T, step_f, j=j, Xs=(A, S))
+                    else:                                   # prox_j(X - dX - step grad_j, step) (nmf.py:181-185)
+                        out = host_f[j](T, step_f)
+                    dev.put(_lib.BUF_TMP_A, j, np.asarray(out))
+                dev.bsdmm_split(j, 1, hf, mask)
+                if mask:
+                    step_g = dt.type(float(r0.steps[j]) * 2.0 * len(host_g[j]))           # utils.get_step_g, identity L (utils.py:269-279)
+                    for i, h in enumerate(host_g[j]):
+                        if h is None:
+                            continue
+                        buf = _lib.BUF_TG0 + j * _lib.MAX_G + i
+                        T = dev._download(buf, rows)
+                        T = np.ascontiguousarray(T if j == 0 else T.T).astype(dt)
+                        out = np.asarray(h(T, step_g))                                   # Z_i = prox_g_i(L X + U_i, step_g_i) (utils.py:295-304)
+                        dev._upload(buf, out if j == 0 else out.T)
+                res = dev.bsdmm_split(j, 2, hf, mask, last_block=(o == len(blocks) - 1))
+                if closures is not None:                    # Gauss-Seidel: the next block's closures see this update
+                    _write_back(dev, A, S)
+            return res
+
+        if slow or _wants_iterates(callback):               # no StopIteration handler (algorithms.py:802)
+            res = _iterate(dev, A, S, max_iter, callback, advance if slow else lambda it: dev.bsdmm_run(1), stop_iteration=False)
         else:
             res = dev.bsdmm_run(max_iter)
             _write_back(dev, A, S)

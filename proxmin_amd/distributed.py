@@ -15,10 +15,10 @@ libpmx phase entry points (HIP kernels).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
-import time
-
 import os
+import time
 
 import numpy as np
 
@@ -227,30 +227,65 @@ def _collectives(comm, dev, rank, world, group):
     return dist
 
 
-class ShardedAdaproxDriver:
+class _ShardedDriver:
+    """What the two iteration loops below share: the engine, the collectives and the group; one iteration (phase 0, ONE
+    collective, phase 1, under S-split the gather of every rank's updated columns); the reading of a halt; the closing flush
+    of a stopping test that is evaluated one iteration late.  `it` counts completed iterations."""
+
+    def __init__(self, engine, group, dist_module):
+        if dist_module is None:
+            _lib.require_torch()
+            import torch.distributed as dist_module
+        self.dist, self.eng, self.group = dist_module, engine, group
+        self.it = 0
+        self.stopped = False
+
+    def _allreduce(self):
+        if getattr(self.eng, "s_split", False):     # S-split: reduce-scatter here, the all-gather follows the update
+            reduce_scatter_sum(self.dist, self.eng.comm_out, self.eng.comm, self.group)
+        else:
+            self.dist.all_reduce(self.eng.comm, op=self.dist.ReduceOp.SUM, group=self.group)
+
+    def _iteration(self, it, args0=(), args1=()):
+        self.eng.phase(0, it, *args0)
+        self._allreduce()
+        self.eng.phase(1, it, *args1)
+        if getattr(self.eng, "s_split", False):     # every rank's updated columns of S (pgm: of the next evaluation point)
+            all_gather_chunks(self.dist, self.eng.st_full, self.group)
+
+    def _read_halt(self, halted, reason):
+        if halted and reason == HALT_CONVERGED:
+            self.stopped = True
+        elif halted and reason == HALT_ERROR:
+            raise _lib.PmxError("the device chain of rank-local kernels reported an error")
+        # HALT_RETRY (this rank fell back after a recoverable kernel fault) / HALT_PEER (another rank did): every rank
+        # stopped before the update of iteration it_done (collective halt flag), the halt is cleared: go on from there
+
+    def _flush(self, *args):
+        """the stopping test of the last iteration has not been evaluated yet (it needs A's global sums)"""
+        self.eng.phase(2, self.it, *args)
+        self._allreduce()
+        self.eng.phase(3, self.it, *args)
+        halted, reason, _, _ = self.eng.chain_status()
+        if halted and reason == HALT_CONVERGED:
+            self.stopped = True
+
+
+class ShardedAdaproxDriver(_ShardedDriver):
     """Iteration loop of the row-sharded adaprox back-end (algorithms.py:365-413 with one all-reduce
     per iteration).  `engine` provides phase(), chain_status(), more_subs() and the `comm` tensor."""
 
     def __init__(self, engine, group=None, check_convergence=True, any_prox=True, prox_max_iter=1000, chunk=None, dist_module=None):
-        if dist_module is None:
-            _lib.require_torch()
-            import torch.distributed as dist_module
-        self.dist = dist_module
-        self.eng = engine
-        self.group = group
+        super().__init__(engine, group, dist_module)
         self.check = bool(check_convergence)
         self.any_prox = bool(any_prox)
         self.prox_max_iter = int(prox_max_iter)
-        if chunk is None:
-            # iterations enqueued between two reads of the device status (each read drains the stream: 8 us per iteration at 16, 2 us at
-            # 64, cfg4's share).  The fused tail decides its proximal loops on the device, so nothing is speculated on and the chunks may
-            # be as long as the single-GPU loop's (pmx_adaprox_run); the chain of tail kernels keeps 16 (its per-iteration records: 64 slots)
-            chunk = None
+        # chunk: iterations enqueued between two reads of the device status (each read drains the stream: 8 us per iteration at 16, 2 us at
+        # 64, cfg4's share).  The fused tail decides its proximal loops on the device, so nothing is speculated on and the chunks may
+        # be as long as the single-GPU loop's (pmx_adaprox_run); the chain of tail kernels keeps 16 (its per-iteration records: 64 slots)
         self._chunk_arg = None if chunk is None else int(chunk)
         self.chunk = self._chunk()
         self.nsub = 2
-        self.it = 0              # completed iterations
-        self.stopped = False
 
     SUB_REC_SLOTS = 64       # per-iteration records of the chain of tail kernels (k_update.hip: sub_rec[it & 63])
 
@@ -264,19 +299,9 @@ class ShardedAdaproxDriver:
             return 64 if fused else 16
         return self._chunk_arg if fused else min(self._chunk_arg, self.SUB_REC_SLOTS - 1)
 
-    def _allreduce(self):
-        if getattr(self.eng, "s_split", False):     # S-split: reduce-scatter here, the all-gather follows the update
-            reduce_scatter_sum(self.dist, self.eng.comm_out, self.eng.comm, self.group)
-        else:
-            self.dist.all_reduce(self.eng.comm, op=self.dist.ReduceOp.SUM, group=self.group)
-
-    def _iteration(self, it, b1):
+    def _enqueue(self, it, b1):
         b1_prev = b1[it - 1]    # b1[-1] at it = 0, like the reference (algorithms.py:213)
-        self.eng.phase(0, it, b1[it], b1_prev, 0)
-        self._allreduce()
-        self.eng.phase(1, it, b1[it], b1_prev, self.nsub)
-        if getattr(self.eng, "s_split", False):
-            all_gather_chunks(self.dist, self.eng.st_full, self.group)      # every rank's updated columns of S
+        super()._iteration(it, (b1[it], b1_prev, 0), (b1[it], b1_prev, self.nsub))
 
     def run(self, n_iter, b1):
         """Advance up to n_iter iterations; b1 is the full per-iteration array (len >= it + n_iter)."""
@@ -284,9 +309,8 @@ class ShardedAdaproxDriver:
         while self.it < target and not self.stopped:
             self.chunk = self._chunk()
             hi = min(target, self.it + self.chunk)
-            first = self.it
-            for it in range(first, hi):
-                self._iteration(it, b1)
+            for it in range(self.it, hi):
+                self._enqueue(it, b1)
             halted, reason, it_done, tau = self.eng.chain_status()
             t_enq = self.nsub
             while halted and reason == HALT_NEED_SUB:
@@ -301,7 +325,7 @@ class ShardedAdaproxDriver:
                 self.eng.more_subs(t_enq, more)
                 t_enq += more
                 for it in range(it_done + 1, hi):
-                    self._iteration(it, b1)
+                    self._enqueue(it, b1)
                 before = it_done
                 halted, reason, it_done, tau = self.eng.chain_status()
                 if it_done > before:
@@ -311,24 +335,13 @@ class ShardedAdaproxDriver:
             self.it = it_done
             if self.any_prox:
                 self.nsub = max(2, min(max(tau), self.prox_max_iter))
-            if halted and reason == HALT_CONVERGED:
-                self.stopped = True
-            elif halted and reason == HALT_ERROR:
-                raise _lib.PmxError("the device chain of rank-local kernels reported an error")
-            # HALT_RETRY (this rank fell back after a recoverable kernel fault) / HALT_PEER (another rank did): every rank
-            # stopped before the update of iteration it_done (collective halt flag), the halt is cleared: go on from there
+            self._read_halt(halted, reason)
         if self.check and not self.stopped and n_iter > 0:
-            # the stopping test of the last iteration has not been evaluated yet (it needs A's global sums)
-            self.eng.phase(2, self.it, 0.0, 0.0, 0)
-            self._allreduce()
-            self.eng.phase(3, self.it, 0.0, 0.0, 0)
-            halted, reason, it_done, tau = self.eng.chain_status()
-            if halted and reason == HALT_CONVERGED:
-                self.stopped = True
+            self._flush(0.0, 0.0, 0)
         return self.it
 
 
-class ShardedLoop:
+class ShardedLoop(_ShardedDriver):
     """Iteration loop of the row-sharded pgm and bsdmm back-ends: phase 0, ONE all-reduce, phase 1.
     pgm evaluates its stopping test one iteration late (A's sums are global only after the next all-reduce)
     and flushes it after the last iteration; bsdmm's all-reduce sits between its A step and its S step, so its
@@ -337,45 +350,20 @@ class ShardedLoop:
     def __init__(self, engine, group=None, deferred_test=True, chunk=32, dist_module=None):
         # chunk: iterations enqueued between two reads of the device status.  After a mid-chunk convergence the rest of the chunk still runs
         # (halted kernels return at once, the collectives are real): 32 bounds that tail at half of round 5's 64 for ~1 us more per iteration
-        if dist_module is None:
-            _lib.require_torch()
-            import torch.distributed as dist_module
-        self.dist, self.eng, self.group = dist_module, engine, group
+        super().__init__(engine, group, dist_module)
         self.deferred = bool(deferred_test)
         self.chunk = int(chunk)
-        self.it = 0
-        self.stopped = False
-
-    def _allreduce(self):
-        if getattr(self.eng, "s_split", False):     # S-split: reduce-scatter here, the all-gather follows the update
-            reduce_scatter_sum(self.dist, self.eng.comm_out, self.eng.comm, self.group)
-        else:
-            self.dist.all_reduce(self.eng.comm, op=self.dist.ReduceOp.SUM, group=self.group)
 
     def run(self, n_iter):
         target = self.it + int(n_iter)
-        split = getattr(self.eng, "s_split", False)
         while self.it < target and not self.stopped:
-            hi = min(target, self.it + self.chunk)
-            for it in range(self.it, hi):
-                self.eng.phase(0, it)
-                self._allreduce()
-                self.eng.phase(1, it)
-                if split:                            # every rank's columns of the next evaluation point
-                    all_gather_chunks(self.dist, self.eng.st_full, self.group)
-            halted, reason, it_done, _ = self.eng.chain_status()
-            self.it = it_done
-            if halted and reason == HALT_CONVERGED:
-                self.stopped = True
-            elif halted and reason == HALT_ERROR:
-                raise _lib.PmxError("the device chain of rank-local kernels reported an error")
+            for it in range(self.it, min(target, self.it + self.chunk)):
+                self._iteration(it)
+            halted, reason, self.it, _ = self.eng.chain_status()
+            self._read_halt(halted, reason)
         if self.deferred and not self.stopped and n_iter > 0:
-            self.eng.phase(2, self.it)
-            self._allreduce()
-            self.eng.phase(3, self.it)
-            halted, reason, _, _ = self.eng.chain_status()
-            self.stopped = bool(halted and reason == HALT_CONVERGED)
-        if split and getattr(self.eng, "st_iterate", None) is not None and n_iter > 0:
+            self._flush()
+        if getattr(self.eng, "s_split", False) and getattr(self.eng, "st_iterate", None) is not None and n_iter > 0:
             all_gather_chunks(self.dist, self.eng.st_iterate, self.group)      # FISTA: the iterate S itself, once per run
         return self.it
 
@@ -478,6 +466,41 @@ def projection_type(seq):
     return all(seq.seq[i].op in box or (seq.seq[i].op in maybe and not seq.seq[i].relative) for i in range(seq.n))
 
 
+def _pair(v):
+    return (v, v) if np.isscalar(v) else tuple(v)
+
+
+@contextlib.contextmanager
+def _session(Y_local, A_local, S, prox_A, prox_S, group, device):
+    """One rank's share of a sharded solve: -> (context with Y and the factors on the device, rank, world, the device
+    sequences of prox_A / prox_S (default prox_plus)).  Kernels and collectives must share a (non-default) stream: torch's
+    collectives order themselves against the CURRENT stream, so ours is made current for the duration of the solve."""
+    torch = _lib.require_torch()
+    import torch.distributed as dist
+    from . import operators
+    from .engine import DeviceNMF
+    seqs = [operators.device_proxseq(operators.prox_plus if q is None else q, j) for j, q in enumerate((prox_A, prox_S))]
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    if device is None:
+        device = torch.cuda.current_device()
+    tstream = torch.cuda.Stream(device=device)
+    with torch.cuda.stream(tstream), DeviceNMF(A_local.shape[0], S.shape[1], A_local.shape[1], device=device,
+                                               stream=tstream.cuda_stream) as dev:
+        dev.set_Y(Y_local)
+        dev.set_factors(A_local, S)
+        yield dev, rank, world, seqs
+
+
+def _finish(dev, A_local, S):
+    """the factors written back in place -> converged per block, as the device's last Result has it"""
+    dA, dS = dev.get_factors()
+    A_local[...] = dA
+    S[...] = dS
+    r = _lib.Result()
+    _lib.check(dev.lib.pmx_iter_result(dev.h, C.byref(r)))
+    return bool(r.converged[0]), bool(r.converged[1])
+
+
 def nmf_adaprox_sharded(Y_local, A_local, S, M_global, prox_A=None, prox_S=None, scheme="adam", b1=0.9, b2=0.999,
                         eps=1e-8, p=0.25, check_convergence=True, e_rel=1e-3, max_iter=1000, prox_max_iter=1000,
                         group=None, device=None, Y_is_device_ptr=None, s_split="auto", comm=None):
@@ -488,31 +511,10 @@ def nmf_adaprox_sharded(Y_local, A_local, S, M_global, prox_A=None, prox_S=None,
     Requires an initialised torch.distributed process group whose backend can reduce CUDA tensors
     (nccl = RCCL).  comm: "torch" (default) issues the collectives through torch.distributed, "native" through the C ABI's own
     RCCL entry points (pmx_comm_*; the process group only hands the communicator id around).  Returns (converged, iterations)."""
-    torch = _lib.require_torch()
-    _lib.require_torch()
-    import torch.distributed as dist
-    from . import operators
-    from .engine import DeviceNMF
-
-    if prox_A is None:
-        prox_A = operators.prox_plus
-    if prox_S is None:
-        prox_S = operators.prox_plus
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
-    if device is None:
-        device = torch.cuda.current_device()
-    seqs = [operators.device_proxseq(prox_A, 0), operators.device_proxseq(prox_S, 1)]
     if not hasattr(b1, "__iter__"):
         b1 = np.array((b1,) * max_iter)
     b1 = np.asarray(b1, dtype=np.float64)
-    e = (e_rel, e_rel) if np.isscalar(e_rel) else tuple(e_rel)
-    # kernels and collectives must share a (non-default) stream: torch's collectives order themselves
-    # against the CURRENT stream, so make ours current for the duration of the solve
-    tstream = torch.cuda.Stream(device=device)
-    with torch.cuda.stream(tstream), DeviceNMF(A_local.shape[0], S.shape[1], A_local.shape[1], device=device,
-                                               stream=tstream.cuda_stream) as dev:
-        dev.set_Y(Y_local)
-        dev.set_factors(A_local, S)
+    with _session(Y_local, A_local, S, prox_A, prox_S, group, device) as (dev, rank, world, seqs):
         # S-split ("auto": whenever it applies): the S update sharded over the ranks between a reduce-scatter and an
         # all-gather instead of replicated behind an all-reduce -- projection-type prox_S, N divisible by the rank count
         can_split = world > 1 and S.shape[1] % world == 0 and projection_type(seqs[1])
@@ -520,17 +522,12 @@ def nmf_adaprox_sharded(Y_local, A_local, S, M_global, prox_A=None, prox_S=None,
             raise NotImplementedError("S-split needs a projection-type prox_S and N divisible by the number of ranks")
         eng = ShardEngine(dev, world, rank, M_global, s_split=bool(s_split) and can_split)
         dev.adaprox_begin(seqs, scheme=scheme, b2=b2, eps=eps, p=p, check_convergence=check_convergence,
-                          prox_max_iter=prox_max_iter, e_rel=e)
+                          prox_max_iter=prox_max_iter, e_rel=_pair(e_rel))
         drv = ShardedAdaproxDriver(eng, group, check_convergence, seqs[0].n > 0 or seqs[1].n > 0, prox_max_iter,
                                    dist_module=_collectives(comm, dev, rank, world, group))
         its = drv.run(max_iter, b1)
-        dA, dS = dev.get_factors()
-        A_local[...] = dA
-        S[...] = dS
-        r = _lib.Result()
-        _lib.check(dev.lib.pmx_iter_result(dev.h, C.byref(r)))
-    conv = (bool(r.converged[0]), bool(r.converged[1])) if check_convergence else (None, None)
-    return conv, its
+        conv = _finish(dev, A_local, S)
+    return conv if check_convergence else (None, None), its
 
 
 def nmf_pgm_sharded(Y_local, A_local, S, M_global, prox_A=None, prox_S=None, accelerated=False, step_scale=1.0,
@@ -540,67 +537,29 @@ def nmf_pgm_sharded(Y_local, A_local, S, M_global, prox_A=None, prox_S=None, acc
     partial Gram matrix and the stopping sums riding in every chunk), each rank updates its N / world columns (and, under
     FISTA, extrapolates them), all-gather of the next evaluation point; any device prox_S (pgm applies it once, row by row of
     S^T).  Returns (converged, iterations)."""
-    torch = _lib.require_torch()
-    _lib.require_torch()
-    import torch.distributed as dist
-    from . import operators
-    from .engine import DeviceNMF
-    prox_A = operators.prox_plus if prox_A is None else prox_A
-    prox_S = operators.prox_plus if prox_S is None else prox_S
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
-    device = torch.cuda.current_device() if device is None else device
-    seqs = [operators.device_proxseq(prox_A, 0), operators.device_proxseq(prox_S, 1)]
-    e = (e_rel, e_rel) if np.isscalar(e_rel) else tuple(e_rel)
-    tstream = torch.cuda.Stream(device=device)
-    with torch.cuda.stream(tstream), DeviceNMF(A_local.shape[0], S.shape[1], A_local.shape[1], device=device,
-                                               stream=tstream.cuda_stream) as dev:
-        dev.set_Y(Y_local)
-        dev.set_factors(A_local, S)
+    with _session(Y_local, A_local, S, prox_A, prox_S, group, device) as (dev, rank, world, seqs):
         can_split = world > 1 and S.shape[1] % world == 0
         if s_split is True and not can_split:
             raise NotImplementedError("S-split needs N divisible by the number of ranks")
         eng = ShardEngine(dev, world, rank, M_global, "pgm", s_split=bool(s_split) and can_split)
-        dev.pgm_begin(seqs, accelerated=accelerated, step_scale=step_scale, fixed_steps=fixed_steps, e_rel=e)
+        dev.pgm_begin(seqs, accelerated=accelerated, step_scale=step_scale, fixed_steps=fixed_steps, e_rel=_pair(e_rel))
         eng.bind_eval_buffer()
         loop = ShardedLoop(eng, group, deferred_test=True, dist_module=_collectives(comm, dev, rank, world, group))
         its = loop.run(max_iter)
-        dA, dS = dev.get_factors()
-        A_local[...] = dA
-        S[...] = dS
-        r = _lib.Result()
-        _lib.check(dev.lib.pmx_iter_result(dev.h, C.byref(r)))
-    return (bool(r.converged[0]), bool(r.converged[1])), its
+        conv = _finish(dev, A_local, S)
+    return conv, its
 
 
 def nmf_bsdmm_sharded(Y_local, A_local, S, M_global, prox_A=None, prox_S=None, proxs_g=None, e_rel=1e-3, e_abs=0.0,
                       max_iter=1000, group=None, device=None, comm=None):
     """Row-sharded `nmf(Y, A, S, algorithm=bsdmm, proxs_g=...)` for one rank.  Returns (converged, iterations)."""
-    torch = _lib.require_torch()
-    _lib.require_torch()
-    import torch.distributed as dist
     from . import operators
-    from .engine import DeviceNMF
-    prox_A = operators.prox_plus if prox_A is None else prox_A
-    prox_S = operators.prox_plus if prox_S is None else prox_S
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
-    device = torch.cuda.current_device() if device is None else device
-    seq_f = [operators.device_proxseq(prox_A, 0), operators.device_proxseq(prox_S, 1)]
     proxs_g = proxs_g or [None, None]
     seq_g = [None if g is None else [operators.device_proxseq(q, j) for q in g] for j, g in enumerate(proxs_g)]
-    er = (e_rel, e_rel) if np.isscalar(e_rel) else tuple(e_rel)
-    ea = (e_abs, e_abs) if np.isscalar(e_abs) else tuple(e_abs)
-    tstream = torch.cuda.Stream(device=device)
-    with torch.cuda.stream(tstream), DeviceNMF(A_local.shape[0], S.shape[1], A_local.shape[1], device=device,
-                                               stream=tstream.cuda_stream) as dev:
-        dev.set_Y(Y_local)
-        dev.set_factors(A_local, S)
+    with _session(Y_local, A_local, S, prox_A, prox_S, group, device) as (dev, rank, world, seq_f):
         eng = ShardEngine(dev, world, rank, M_global, "bsdmm")
-        dev.bsdmm_begin(seq_f, seq_g, e_rel=er, e_abs=ea)
+        dev.bsdmm_begin(seq_f, seq_g, e_rel=_pair(e_rel), e_abs=_pair(e_abs))
         loop = ShardedLoop(eng, group, deferred_test=False, dist_module=_collectives(comm, dev, rank, world, group))
         its = loop.run(max_iter)
-        dA, dS = dev.get_factors()
-        A_local[...] = dA
-        S[...] = dS
-        r = _lib.Result()
-        _lib.check(dev.lib.pmx_iter_result(dev.h, C.byref(r)))
-    return [bool(r.converged[0]), bool(r.converged[1])], its
+        conv = _finish(dev, A_local, S)
+    return list(conv), its

@@ -230,7 +230,7 @@ def _nmf_sharded(Y, A, S, W, prox_A, prox_S, algorithm, step, max_iter, e_rel, c
     group, comm, s_split = kw.pop("group", None), kw.pop("comm", None), kw.pop("s_split", "auto")
     if not (np.isscalar(W) and W == 1):
         raise NotImplementedError("row-sharded nmf(): a weighted likelihood is not carried by the sharded protocol")
-    if callback is not None and not isinstance(callback, utils_NullCallback()):
+    if algorithms._wants_iterates(callback):
         raise NotImplementedError("row-sharded nmf(): a callback would see one rank's rows of A only")
     assert np.asarray(A).shape[0] <= M_global
     if algorithm is algorithms.pgm:
@@ -269,11 +269,6 @@ def _nmf_sharded(Y, A, S, W, prox_A, prox_S, algorithm, step, max_iter, e_rel, c
     if kw:
         raise TypeError("unexpected arguments for row-sharded bsdmm: %r" % sorted(kw))
     return conv
-
-
-def utils_NullCallback():
-    from .utils import NullCallback
-    return NullCallback
 
 
 def nmf(

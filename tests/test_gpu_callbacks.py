@@ -571,3 +571,91 @@ def test_barzilai_borwein_stepper_called_as_a_function(pm):
                 assert isinstance(out, tuple) if it == 0 else isinstance(out, np.ndarray)
                 np.testing.assert_allclose(np.asarray(out, dtype=np.float64), z["bb%d/steps" % typ][it], rtol=rtol, err_msg="type %d call %d %s" % (typ, it, dt.__name__))
             assert bb.X_[0].dtype == dt and bb.G_ is G
+
+
+def _fixture_33x47(dtype):
+    z, _ = load_golden("nmf_33x47_k3_f64.npz")
+    return tuple(z["inputs_plain/" + k].astype(dtype) for k in ("Y", "A0", "S0"))
+
+
+def _host_route_calls(pm, Y, A0, S0):
+    """route -> call(A, S, max_iter, callback) of the per-iteration host routes of pgm and adaprox"""
+    ops, nmf = pm.operators, pm.nmf
+    grad, f = partial(nmf.grad_likelihood, Y=Y), partial(nmf.log_likelihood, Y=Y)
+    lip = nmf.step_pgm(A0, S0)
+
+    def half(*X, it=None):
+        return tuple(0.5 * s for s in nmf.step_pgm(*X))
+
+    def long_step(*X, it=None):                      # 1.5 x the Lipschitz steps: the line search has something to halve
+        return tuple(1.5 * s for s in nmf.step_pgm(*X))
+
+    def pgm(**kw):
+        kw.setdefault("step", partial(nmf.step_pgm, W=1))
+        kw.setdefault("prox", [ops.prox_plus] * 2)
+        return lambda A, S, max_iter, callback: pm.pgm([A, S], grad, kw["step"], e_rel=1e-12, max_iter=max_iter, callback=callback,
+                                                       **{k: v for k, v in kw.items() if k != "step"})
+
+    def ada(**kw):
+        kw.setdefault("prox", [ops.prox_plus] * 2)
+        return lambda A, S, max_iter, callback: pm.adaprox([A, S], grad, nmf.step_adaprox, e_rel=1e-12, max_iter=max_iter, callback=callback, **kw)
+    return {"pgm_callback": pgm(), "pgm_user_prox": pgm(prox=[my_plus, ops.prox_plus]), "pgm_user_step": pgm(step=half),
+            "pgm_bt_user_step": pgm(step=long_step, backtracking=True, f=f),
+            "pgm_bt_user_prox": pgm(step=nmf.constant_step(4 * lip[0], 4 * lip[1]), prox=[my_plus, ops.prox_plus], backtracking=True, f=f),
+            "adaprox_callback": ada(), "adaprox_user_prox": ada(prox=[ops.prox_plus, my_plus])}
+
+
+def _flat(ret):
+    """the arrays and scalars of a solver's return value, in order"""
+    out = []
+    for v in ret:
+        out.extend(_flat(v) if isinstance(v, (tuple, list)) else [v])
+    return out
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("route", ["pgm_callback", "pgm_user_prox", "pgm_user_step", "pgm_bt_user_step", "pgm_bt_user_prox",
+                                   "adaprox_callback", "adaprox_user_prox"])
+def test_stop_iteration_at_3_equals_max_iter_3(pm, route, dtype):
+    """A callback that raises StopIteration at it = 3 ends the run after three iterations, on every per-iteration host route:
+    A, S and the returned tuple are BIT-IDENTICAL to the same call with max_iter=3 and no callback (33 x 47, K = 3 fixture)."""
+    Y, A0, S0 = _fixture_33x47(dtype)
+    call = _host_route_calls(pm, Y, A0, S0)[route]
+    A, S = A0.copy(), S0.copy()
+    seen = []
+
+    def stop_at_3(*X, it=None):
+        seen.append(it)
+        if it == 3:
+            raise StopIteration
+    ret = call(A, S, 10, stop_at_3)
+    A3, S3 = A0.copy(), S0.copy()
+    ret3 = call(A3, S3, 3, None)
+    # three iterations ran and moved the iterate (A: on this input the line search holds S in place, T_S collapses as in the reference)
+    assert seen == [0, 1, 2, 3] and not np.array_equal(A, A0)
+    assert np.array_equal(A, A3) and np.array_equal(S, S3)
+    got, want = _flat(ret), _flat(ret3)
+    assert len(got) == len(want) and len(got) >= 5
+    for g, w in zip(got, want):
+        assert type(g) is type(w) and np.array_equal(g, w), (route, g, w)
+
+
+@pytest.mark.parametrize("user_prox", [False, True], ids=["callback_only", "user_prox"])
+def test_bsdmm_stop_iteration_propagates(pm, user_prox):
+    """bsdmm has no StopIteration handler (algorithms.py:802): the callback's exception reaches the caller AS StopIteration, and A and
+    S hold the iterate of the last completed iteration -- the one the raising callback was shown, equal to a run of three iterations."""
+    Y, A0, S0 = _fixture_33x47(np.float32)
+    prox_A = my_plus if user_prox else pm.operators.prox_plus
+    shown = {}
+
+    def stop(*X, it=None):
+        if it == 3:
+            shown["A"], shown["S"] = X[0].copy(), X[1].copy()
+            raise StopIteration
+    A, S = A0.copy(), S0.copy()
+    with pytest.raises(StopIteration):
+        pm.nmf.nmf(Y, A, S, algorithm=pm.bsdmm, prox_A=prox_A, max_iter=10, e_rel=1e-12, callback=stop)
+    assert np.array_equal(A, shown["A"]) and np.array_equal(S, shown["S"])
+    A3, S3 = A0.copy(), S0.copy()
+    pm.nmf.nmf(Y, A3, S3, algorithm=pm.bsdmm, prox_A=prox_A, max_iter=3, e_rel=1e-12)
+    assert not np.array_equal(A, A0) and np.array_equal(A, A3) and np.array_equal(S, S3)
