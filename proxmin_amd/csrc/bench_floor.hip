@@ -36,6 +36,10 @@ __global__ void kf_fill(float* p, size_t n, unsigned seed, int zero) {
 // FETCH: 0 = 4 bytes per lane (the accumulator layout: 2 rows x 128 B per wave-instruction), 1 = 8 bytes per lane for a PAIR of blocks (k_grad_f16_v8's
 // fetch: adjacent columns belong to the two blocks of a pair, 256 B per row and instruction), 2 = 16 bytes per lane (8 rows x 128 B per instruction),
 // 3 = no loads.  Four blocks of Y in flight per producer wave in every mode (64 registers: what K1's producers hold).
+// [r7] 4 = 16 bytes per lane SPANNING the pair (k_grad_f16_v8<.., Y16>'s fetch: the even lane of a lane pair requests the pair's four adjacent columns for row r, the
+// odd lane for row r + 1, and the two swap halves -- one quad_perm:[1,0,3,2] exchange inside a select per value where the value is used; 4 rows x 256 B per
+// instruction), its requests issued as K1 issues them: a pair's eight spread over the MFMAs of a slot, two in front of each.  5 = fetch 1 issued the same way (four
+// 8-byte requests in front of each MFMA) -- the like-for-like partner of 4; fetch 1 itself issues a pair's sixteen in one burst.
 // MFP / MFC: MFMAs per block of a producer wave / of a consumer wave (two accumulators: 2 x MFC).  OPS: 0 constant operand registers, 2 one fresh 16-byte
 // fragment of pseudo-random fp16 data read from LDS per MFMA.  EPI: the producers also run ~4 VALU per value of the tile and write two fp16 images.
 template <int FETCH, int MFP, int MFC, int OPS, bool EPI>
@@ -67,6 +71,35 @@ __global__ __launch_bounds__(512, 2) void k_floor(const float* __restrict__ Y, i
     const f16x8* fragw = reinterpret_cast<const f16x8*>(smem + 65536) + lane;     // + 64 * n: conflict-free 16-byte reads
     float y[FETCH == 3 ? 1 : 4][16] = {};
     auto block_rc = [&](int t, int& rp, int& cb) { const int tc = t < T ? t : T - 1; rp = tc / NCB; cb = tc % NCB; };
+    const bool oddl = (lane & 1) != 0;
+    auto y_get = [&](int b, int i) {     // row i of block b as the epilogue wants it (FETCH 4: the exchange with the neighbouring lane)
+        if constexpr (FETCH == 4) {
+            const float x0 = y[b][i & ~1], x1 = y[b][i | 1];
+            const float n = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (i & 1) ? x0 : x1), 0xB1, 0xf, 0xf, true));
+            return (i & 1) ? (oddl ? x1 : n) : (oddl ? n : x0);
+        } else return y[b][i];
+    };
+    auto issue_part = [&](int buf, int t, int part) {   // FETCH 4 / 5: rows 4 part .. 4 part + 3 of the pair (t, t + 1), t even, into buf, buf + 1
+        if (!producer) return;
+        int rp, cb;
+        block_rc(t, rp, cb);
+        if constexpr (FETCH == 4) {
+            const float* src = Y + (int64_t)(row0 + rp * 128 + w * 32 + 4 * hi + (l31 & 1)) * ld + col0 + (cb >> 1) * 64 + 4 * (l31 >> 1);
+#pragma unroll
+            for (int u = 2 * part; u < 2 * part + 2; ++u) {
+                const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(&src[(int64_t)(2 * (u & 1) + 8 * (u >> 1)) * ld]));
+                y[buf][2 * u] = v[0]; y[(buf + 1) & 3][2 * u] = v[1]; y[buf][2 * u + 1] = v[2]; y[(buf + 1) & 3][2 * u + 1] = v[3];
+            }
+        } else if constexpr (FETCH == 5) {
+            const float* src = Y + (int64_t)(row0 + rp * 128 + w * 32 + 4 * hi) * ld + col0 + (cb >> 1) * 64 + 2 * l31;
+#pragma unroll
+            for (int i = 4 * part; i < 4 * part + 4; ++i) {
+                const f32x2 v = __builtin_nontemporal_load(reinterpret_cast<const f32x2*>(&src[(int64_t)((i & 3) + 8 * (i >> 2)) * ld]));
+                y[buf][i] = v[0];
+                y[(buf + 1) & 3][i] = v[1];
+            }
+        }
+    };
     auto issue = [&](int buf, int t) {   // FETCH 0 / 2: block t into buffer buf (= t & 3, a compile-time constant at every call); FETCH 1: the pair (t, t + 1), t even, into buf, buf + 1
         if (!producer) return;
         int rp, cb;
@@ -93,19 +126,22 @@ __global__ __launch_bounds__(512, 2) void k_floor(const float* __restrict__ Y, i
         }
     };
     if constexpr (FETCH == 1) { issue(0, 0); issue(2, 2); }
-    else if constexpr (FETCH != 3) { issue(0, 0); issue(1, 1); issue(2, 2); issue(3, 3); }
+    else if constexpr (FETCH >= 4) {
+#pragma unroll
+        for (int part = 0; part < 4; ++part) { issue_part(0, 0, part); issue_part(2, 2, part); }
+    } else if constexpr (FETCH != 3) { issue(0, 0); issue(1, 1); issue(2, 2); issue(3, 3); }
     for (int t = 0; t < T; t += 4) {
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
             if (producer) {
                 if constexpr (FETCH != 3) {
 #pragma unroll
-                    for (int i = 0; i < 16; ++i) acc += y[d][i];
+                    for (int i = 0; i < 16; ++i) acc += y_get(d, i);
                 }
                 if constexpr (EPI) {      // an epilogue's worth: ~4 VALU per value of the tile, two fp16 images written
                     float r[16];
 #pragma unroll
-                    for (int i = 0; i < 16; ++i) { const float x = y[FETCH == 3 ? 0 : d][i] * 1.0001f - acc; r[i] = x * 0.5f + (float)(_Float16)x; }
+                    for (int i = 0; i < 16; ++i) { const float x = y_get(FETCH == 3 ? 0 : d, i) * 1.0001f - acc; r[i] = x * 0.5f + (float)(_Float16)x; }
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         f16x4 h, l;
@@ -117,14 +153,19 @@ __global__ __launch_bounds__(512, 2) void k_floor(const float* __restrict__ Y, i
                 }
             }
             if constexpr (FETCH == 1) { if (d & 1) issue((d + 3) & 3, t + d + 3); }      // the pair (t + d - 1, t + d) is free: blocks t + d + 3, t + d + 4
+            else if constexpr (FETCH >= 4) {}                                             // (in front of the producers' MFMAs, below)
             else if constexpr (FETCH != 3) issue(d, t + d + 4);
             const int t0 = (t + d) * 7;
             if (producer) {
                 f16x8 b = fb;
 #pragma unroll
                 for (int q = 0; q < MFP; ++q) {
+                    if constexpr (FETCH >= 4 && MFP == 4) {
+                        if (d & 1) { issue_part((d + 3) & 3, t + d + 3, q); __builtin_amdgcn_sched_barrier(0); }
+                    }
                     if constexpr (OPS != 0) b = fragw[64 * ((t0 + q) & 63)];
                     c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa, b, c0, 0, 0, 0);
+                    if constexpr (FETCH >= 4 && MFP == 4) { if (d & 1) __builtin_amdgcn_sched_barrier(0); }
                 }
             } else {
                 f16x8 x = fa, z = fb;
@@ -298,7 +339,7 @@ static int time_launches(Kern kern, int lds, int grid, int reps, const float* Y,
 extern "C" const char* pmxf_last_error() { return g_err; }
 
 // K1's skeleton on a fresh M x N fp32 matrix (M % 2048 == 0, N % 2048 == 0; 16384 x 16384 = cfg3), average ms per launch over 2 x reps launches.
-// variant = fetch + 10 * ops + 100 * epi + 1000 * mfma   (fetch 0..3 as FETCH; ops 0 / 2; epi 0 / 1; mfma 0: none, 1: today's 4 + 24, 2: round 3's 12 + 24, 3: K = 128's 8 + 48, 4: a one-gradient pass's 4 + 12)
+// variant = fetch + 10 * ops + 100 * epi + 1000 * mfma   (fetch 0..5 as FETCH; ops 0 / 2; epi 0 / 1; mfma 0: none, 1: today's 4 + 24, 2: round 3's 12 + 24, 3: K = 128's 8 + 48, 4: a one-gradient pass's 4 + 12)
 extern "C" int pmxf_stream(int device, int variant, int M, int N, int zero_data, int reps, double* ms) {
     if (!ms || M <= 0 || N <= 0 || M % 2048 || N % 2048 || reps <= 0) { snprintf(g_err, sizeof g_err, "bad arguments"); return -1; }
     FCHECK(hipSetDevice(device));
@@ -328,6 +369,10 @@ extern "C" int pmxf_stream(int device, int variant, int M, int N, int zero_data,
     case 1012: VAR(2, 4, 12, 2, false); break;
     case 1111: VAR(1, 4, 12, 2, true); break;    // + an epilogue's VALU and LDS stores
     case 1112: VAR(2, 4, 12, 2, true); break;
+    case 1014: VAR(4, 4, 12, 2, false); break;   // [r7] the pair-spanning 16-byte fetch with its exchange, requests spread over the slot
+    case 1015: VAR(5, 4, 12, 2, false); break;   //      the 8-byte fetch spread the same way
+    case 1114: VAR(4, 4, 12, 2, true); break;
+    case 1115: VAR(5, 4, 12, 2, true); break;
     case 3011: VAR(1, 8, 24, 2, false); break;   // [r6] K = 128 (k_grad_f16_k128<HH, RS>): 8 + 48 MFMAs per producer + consumer wave and 128 x 32 block
     case 3013: VAR(3, 8, 24, 2, false); break;   //      ... its MFMAs alone
     case 4011: VAR(1, 4, 6, 2, false); break;    // [r6] a one-gradient pass at K = 64 (bsdmm's K1s): 4 + 12

@@ -871,6 +871,7 @@ struct GradV4Args {
     int r3;              // [r4] k_grad_f16_v8<.., R3>: third terms of A and S in the residual's product, two accumulators
     int consPrio;        // [r6] s_setprio level of the CONSUMER waves for the launch (0: none): the consumers are the pole of every slot, the producers wait ~30 % of it at the barrier
     K1GramFold fold;     // [r6] k_grad_f16_k32: the step rule's Gram fold riding in the first workgroups (pmx_common.h)
+    int y16;             // [r7] k_grad_f16_v8<.., HH>: Y can be fetched sixteen bytes per lane (ldY % 4 == 0, 16-byte-aligned base): the <.., Y16> instances
 };
 
 // (k_grad_bf16_v4's kernel was removed in round 4 together with k_grad_bf16_v5's: with K1's zero-padded frame -- pmx_k1_frame -- the

@@ -162,8 +162,15 @@ static_assert(V8_LDS_BYTES <= 160 * 1024, "");
 // gSt needs no merge of row halves at the end.  Passes that want ONE gradient keep the row split (two of four waves would idle).
 // ONLYS [r5]: the pass wants gSt alone (bsdmm's S step).  The row split's consumers then hold no gA tiles, and the 32 registers they leave keep each wave's share
 // of the panel's A fragments for the panel's eight slots: 8 of the 16 KB a consumer reads per slot.
-template <bool PROF, bool HASW, bool CHAIN, bool LOSS, bool R3 = false, bool HH = false, bool RS = false, bool ONLYS = false>
+// Y16 [r7]: the producers fetch Y SIXTEEN bytes per lane (the <HH> instances on a Y whose pitch and base allow it: GradV4Args::y16).  The column map stays: four
+// adjacent columns 4 m .. 4 m + 3 of a pair's span are (block 2q, n = 2 m), (2q + 1, 2 m), (2q, 2 m + 1), (2q + 1, 2 m + 1) -- the columns of the two neighbouring
+// lanes l31 = 2 m, 2 m + 1.  The even lane loads them for row r, the odd lane for row r + 1, and the two swap halves (one v_cndmask_b32_dpp quad_perm:[1,0,3,2]
+// per value, in the epilogue step that reads the value): eight global_load_dwordx4 per block pair instead of sixteen dwordx2, each 4 rows x 256
+// contiguous bytes, eight offset registers instead of sixteen, still 64 registers of Y in flight.  Every Y value reaches the subtraction it reached before:
+// gradients bit for bit those of the 8-byte fetch.
+template <bool PROF, bool HASW, bool CHAIN, bool LOSS, bool R3 = false, bool HH = false, bool RS = false, bool ONLYS = false, bool Y16 = false>
 __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
+    static_assert(!Y16 || (HH && !PROF && !LOSS), "Y16: the <HH> gradient passes (W shares Y's sixteen offsets: weighted instances keep the 8-byte fetch)");
     static_assert(!ONLYS || (HH && !RS && !CHAIN && !PROF && !LOSS), "ONLYS: an instance of the <HH> gradient pass without gA");
     static_assert(!(R3 && HH) && !(HH && HASW), "HH: unweighted contexts, instead of the third terms");
     static_assert(!RS || (HH && !PROF && !LOSS), "RS: an instance of the <HH> gradient pass");
@@ -304,9 +311,15 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
         // measured, not used.)  Nontemporal: Y is read once per launch; keeping it out of L2 / MALL leaves the gradient
         // slabs this kernel writes there for the update kernel that folds them (iteration -2.7 % at 16384 x 16384).
         typedef float f32x2 __attribute__((ext_vector_type(2)));
-        unsigned yoff[16];
+        typedef float f32x4 __attribute__((ext_vector_type(4)));
+        unsigned yoff[Y16 ? 8 : 16];
+        if constexpr (Y16) {                 // load u: rows e = 2 u (even lanes) and 2 u + 1 (odd lanes) of the tile, the lane PAIR's four columns
 #pragma unroll
-        for (int i = 0; i < 16; ++i) yoff[i] = ((unsigned)((i & 3) + 8 * (i >> 2) + 4 * hi) * (unsigned)a.ldY + 2u * (unsigned)l31) * 4u;
+            for (int u = 0; u < 8; ++u) yoff[u] = ((unsigned)(2 * (u & 1) + (l31 & 1) + 8 * (u >> 1) + 4 * hi) * (unsigned)a.ldY + 4u * (unsigned)(l31 >> 1)) * 4u;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) yoff[i] = ((unsigned)((i & 3) + 8 * (i >> 2) + 4 * hi) * (unsigned)a.ldY + 2u * (unsigned)l31) * 4u;
+        }
         const float* ybase0 = a.Y + (int64_t)(row0 + jw * 32) * a.ldY + col0;
         const float* wbase0 = HASW ? a.W + (int64_t)(row0 + jw * 32) * a.ldW + col0 : nullptr;   // (ldW == ldY: the launch checks it; W shares Y's offsets)
         // Y (and W) of the block pair q = blocks 2 q, 2 q + 1 (clamped past the end of the region) into pair set `set`:
@@ -319,6 +332,18 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
         };
         auto load_pair_rows = [&](const char* base, const char* basew, auto set_c, auto i0_c, auto n_c) {
             constexpr int set = decltype(set_c)::value, i0 = decltype(i0_c)::value, n = decltype(n_c)::value;
+            if constexpr (Y16) {             // as loaded: elements 0, 1 in row 2 u's registers, 2, 3 in row 2 u + 1's; y_swap() finishes the exchange
+                static_assert(i0 % 2 == 0 && n % 2 == 0, "");
+#pragma unroll
+                for (int u = i0 / 2; u < (i0 + n) / 2; ++u) {
+                    asm volatile("" : "+v"(yoff[u]));
+                    const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(base + yoff[u]));
+                    yv[set][0][2 * u] = v[0];
+                    yv[set][1][2 * u] = v[1];
+                    yv[set][0][2 * u + 1] = v[2];
+                    yv[set][1][2 * u + 1] = v[3];
+                }
+            } else {
 #pragma unroll
             for (int i = i0; i < i0 + n; ++i) {
                 asm volatile("" : "+v"(yoff[i]));
@@ -326,7 +351,21 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
                 yv[set][0][i] = v[0];
                 yv[set][1][i] = v[1];
             }
+            }
             (void)basew;
+        };
+        // Y16: rows 2 u, 2 u + 1 of one tile as the epilogue wants them, from the registers as loaded (x0: element 0 / 1, x1: element 2 / 3 of this lane's
+        // request).  Even lane (its column; row 2 u is its own request): x0 and the neighbour's x0; odd lane: the neighbour's x1 and x1.  ONE instruction per
+        // value: v_cndmask_b32_dpp selects between its own operand and the neighbour's (quad_perm:[1,0,3,2]) under vcc -- the even lanes, then the odd ones.
+        // hipcc has no such pattern (update_dpp + ?: came out as v_mov_b32_dpp + v_cndmask_b32, two per value: 1 % of the iteration, profiles/y16_ab.txt).
+        // The s_mov / s_nop in front are also the two wait states a DPP read wants behind a VALU write of its source, should the compiler have copied one.
+        const unsigned long long evenl = 0x5555555555555555ull;
+        auto y_swap = [&](float x0, float x1, float& y0, float& y1) {
+            asm("s_mov_b64 vcc, %4\n\ts_nop 0\n\t"
+                "v_cndmask_b32_dpp %0, %3, %2, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                "s_not_b64 vcc, vcc\n\t"
+                "v_cndmask_b32_dpp %1, %2, %3, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+                : "=&v"(y0), "=&v"(y1) : "v"(x0), "v"(x1), "s"(evenl) : "vcc", "scc");
         };
         auto load_w_rows = [&](const char* basew, auto i0_c, auto n_c) {      // the ONE set of weights
             constexpr int i0 = decltype(i0_c)::value, n = decltype(n_c)::value;
@@ -494,11 +533,13 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
                 if constexpr (EPI) {
                     if (t < 8) {
                         const int g = t >> 1, hf = t & 1;
-                        float r[2];
+                        float r[2], yq[2];
+                        if constexpr (Y16) y_swap(yv[pset][ptile][2 * t], yv[pset][ptile][2 * t + 1], yq[0], yq[1]);
+                        else { yq[0] = yv[pset][ptile][2 * t]; yq[1] = yv[pset][ptile][2 * t + 1]; }
 #pragma unroll
                         for (int q = 0; q < 2; ++q) {
                             const int e = 4 * g + 2 * hf + q;
-                            r[q] = pp[e] * unP - yv[pset][ptile][e];
+                            r[q] = pp[e] * unP - yq[q];
                             if constexpr (R3) r[q] = __builtin_fmaf(lp[e], unP, r[q]);     // (P_hh - Y) + P_lo
                             if constexpr (HASW) {
                                 const float ww = wv[ptile][e];
@@ -988,18 +1029,27 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
 #undef PH
 }
 
-template <bool PROF, bool HASW, bool CHAIN, bool LOSS, bool R3 = false, bool HH = false, bool RS = false, bool ONLYS = false>
+template <bool PROF, bool HASW, bool CHAIN, bool LOSS, bool R3 = false, bool HH = false, bool RS = false, bool ONLYS = false, bool Y16 = false>
 static hipError_t grad_launch_f16_v8_t(const GradV4Args& a, hipStream_t stream) {
     constexpr int lds = R3 ? V7_LDS_BYTES : V8_LDS_BYTES;        // (three S terms: the split-bf16 kernel's 160 KB)
-    hipError_t e = hipFuncSetAttribute((const void*)k_grad_f16_v8<PROF, HASW, CHAIN, LOSS, R3, HH, RS, ONLYS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipError_t e = hipFuncSetAttribute((const void*)k_grad_f16_v8<PROF, HASW, CHAIN, LOSS, R3, HH, RS, ONLYS, Y16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_grad_f16_v8<PROF, HASW, CHAIN, LOSS, R3, HH, RS, ONLYS>), dim3(a.gridX * a.gridY), dim3(V5_THREADS), lds, stream, a);
+    hipLaunchKernelGGL((k_grad_f16_v8<PROF, HASW, CHAIN, LOSS, R3, HH, RS, ONLYS, Y16>), dim3(a.gridX * a.gridY), dim3(V5_THREADS), lds, stream, a);
     return hipGetLastError();
 }
 // inst (k1_instance): K1_HH, K1_R3 or K1_PLAIN
 static hipError_t grad_launch_f16_v8(const GradV4Args& a, K1Inst inst, hipStream_t stream) {
     if (inst == K1_HH) {             // [r5] the high x high residual whose missing terms arrive as a correction slab
         const bool split = !(getenv("PMX_K1_ROLE_SPLIT") && atoi(getenv("PMX_K1_ROLE_SPLIT")) == 0);     // (PMX_K1_ROLE_SPLIT=0: A/B)
+        // [r7] <Y16>: Y sixteen bytes per lane where its pitch and base allow it (PMX_K1_Y16=0: the 8-byte fetch, for A/B runs and the tests)
+        const bool y16 = a.y16 && !a.prof && !(getenv("PMX_K1_Y16") && atoi(getenv("PMX_K1_Y16")) == 0);
+        if (y16) {
+            if (split && (a.doA & 1) && a.doS)
+                return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, false, true, true, false, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, false, true, true, false, true>(a, stream);
+            if (split && !(a.doA & 1) && a.doS)
+                return grad_launch_f16_v8_t<false, false, false, false, false, true, false, true, true>(a, stream);
+            return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, false, true, false, false, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, false, true, false, false, true>(a, stream);
+        }
         if (split && (a.doA & 1) && a.doS && !a.prof)   // <RS>: both gradients wanted
             return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, false, true, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, false, true, true>(a, stream);
         if (split && !(a.doA & 1) && a.doS)             // <ONLYS>: gSt alone

@@ -1282,6 +1282,7 @@ static int enqueue_grad_once(pmx_ctx* c, const float* A, const float* St, int do
             // anything else runs k_grad_bf16_v7 on the same frame
             c->k1_pairs = (c->ldY % 2) == 0 && (((uintptr_t)c->Y) & 7) == 0 && (c->W == nullptr || (c->ldW == c->ldY && (((uintptr_t)c->W) & 7) == 0));
             inst = k1_instance(c->k1, c->f16_r3, c->W != nullptr, grad, c->k1_pairs);
+            g.y16 = c->k1_pairs && (c->ldY % 4) == 0 && (((uintptr_t)c->Y) & 15) == 0;     // the <HH> instances then fetch sixteen bytes per lane
         }
         if (c->chainL > 0) rc = chain_arm(c, g);     // k_grad_f16_v8<.., CHAIN> / k_grad_bf16_v7<.., CHAIN>
         const bool v8 = c->k1 == K1_F16_V8 && inst != K1_V7;
