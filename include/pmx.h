@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PMX_ABI_VERSION 5
+#define PMX_ABI_VERSION 6
 
 /* ---- status codes -------------------------------------------------------------------- */
 enum {
@@ -209,6 +209,22 @@ int pmx_upload_f64(pmx_ctx* ctx, int buf, const double* host, int64_t count);
 int pmx_download_f64(pmx_ctx* ctx, int buf, double* host, int64_t count);
 /* device address of a buffer (for zero-copy interop, e.g. torch.distributed on the comm buffer) */
 int pmx_buffer_ptr(pmx_ctx* ctx, int buf, void** dptr, int64_t* count);
+/* [ABI v6] One block of a two-block buffer from / to an array that already lives in HBM on the context's device (a torch tensor,
+ * a CuPy array), device to device: pmx_upload / pmx_download without the host.  `buf` is any id pmx_upload takes; its block gives the
+ * logical shape IN THE REFERENCE'S ORIENTATION -- M x K for an A-side buffer, K x N for an S-side one (the context keeps S^T: the
+ * transposition happens in the kernel, csrc/k_xfer.hip).  `dptr` is the address of element (0, 0), stride0 / stride1 the ELEMENT strides
+ * of the two axes: one of them is 1 and the other at least the extent it steps over (row- or column-major with any pitch; the stride of
+ * an axis of extent 1 is not looked at), else PMX_E_INVALID, as for NULL.  `is_f64` says what the array holds and must be what the
+ * context computes in (PMX_MODE_F64 / _F64_MFMA: float64, every other mode: float32), else PMX_E_UNSUPPORTED.  The copy is bit-exact.
+ * pmx_factor_to_device writes the logical elements only: pitch padding and everything before or behind the view keep their bits.
+ * Ordering: an array interface carries no stream, and the context's private stream does not wait for the caller's.
+ *   pmx_factor_from_device  calls hipDeviceSynchronize() on the context's device before its kernel: work that ANY stream enqueued on
+ *                           the array before the call is finished; the copy is complete when the call returns.  It clears the
+ *                           same cached-state flags as pmx_upload.
+ *   pmx_factor_to_device    synchronises the context's stream before it returns: the array may be used on any stream afterwards.
+ * The caller must not touch the array (nor free it) while either call runs. */
+int pmx_factor_from_device(pmx_ctx* ctx, int buf, const void* dptr, int64_t stride0, int64_t stride1, int is_f64);
+int pmx_factor_to_device(pmx_ctx* ctx, int buf, void* dptr, int64_t stride0, int64_t stride1, int is_f64);
 
 /* ---- measurement --------------------------------------------------------------------------
  * With timing on, launches of the fused residual-gradient kernel (K1) are bracketed by HIP events

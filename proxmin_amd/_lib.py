@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("PMX_LIB") or os.path.join(_HERE, "libpmx.so")   # PMX
 MAX_SEQ = 4
 MAX_G = 4
 MAXK = 128
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # enums (include/pmx.h)
 MODE_F32, MODE_BF16X3, MODE_F16X2, MODE_F64, MODE_F16X2R, MODE_F64_MFMA = 0, 2, 3, 4, 5, 6
@@ -118,6 +118,8 @@ _SIGNATURES = {
     "pmx_comm_layout_split": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pmx_set_comm_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "pmx_buffer_ptr": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "pmx_factor_from_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
+    "pmx_factor_to_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
     "pmx_bsdmm_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_double, C.POINTER(Result)]),
     "pmx_pgm_step_arrays": (C.c_int, [C.c_void_p, C.c_int]),
     "pmx_pgm_set_fixed_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),

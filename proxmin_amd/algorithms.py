@@ -28,7 +28,8 @@ from functools import partial
 import numpy as np
 
 from . import _lib, operators, utils
-from .engine import DeviceNMF, open_weighted, as_device_array, DeviceArrayRef, f64_applies
+from .engine import (DeviceNMF, open_weighted, as_device_array, DeviceArrayRef, f64_applies, DeviceFactorRef, as_device_factor, factor_pair, factor_owner,
+                     device_of, refuse_f64_factors)
 
 logger = logging.getLogger("proxmin")
 
@@ -46,11 +47,13 @@ def _problem_from_grad(X, grad):
 
     X = utils._as_tuple(X)
     assert len(X) == 2, "X must be [A, S]"
-    A, S = X
+    A, S = factor_pair(*X)                # factors that live in HBM: engine.DeviceFactorRef (shape, NumPy dtype, element strides)
     assert A.ndim == 2 and S.ndim == 2 and A.shape[1] == S.shape[0]
     if not _is_nmf_grad(grad):
         if not callable(grad):
             raise TypeError("grad must be callable")
+        if isinstance(A, DeviceFactorRef):
+            raise NotImplementedError("device-resident factors with a user-defined `grad` (%r): the callable takes host arrays" % (grad,))
         _warn_host_path("grad (%r)" % (grad,))
         return None, A, S, None
     kw = grad.keywords
@@ -58,7 +61,28 @@ def _problem_from_grad(X, grad):
     if Y is None:
         Y = np.asarray(kw["Y"])
     assert tuple(Y.shape) == (A.shape[0], S.shape[1]), "Y must be M x N"
+    device_of(Y, A)                       # (Y and the factors on two GPUs: ValueError before anything runs)
     return Y, A, S, _nmf._weights(kw.get("W", 1), Y.shape)
+
+
+def _refuse_host_callables(A, step=None, host_prox=()):
+    """Factors that live in HBM go with an iteration that stays on the device: a user `step` or `prox` takes host arrays, and so
+    does this library's prox_unity* along a factor's long axis wherever it is not fused (adaprox, bsdmm, pgm's host route)."""
+    if not isinstance(A, DeviceFactorRef):
+        return
+    if step is not None:
+        raise NotImplementedError("device-resident factors with a user-defined `step` (%r): the callable takes host arrays" % (step,))
+    for j, h in host_prox:                # (block, what _seq_or_host left for the host)
+        if h is None:
+            continue
+        try:
+            operators.device_proxseq(h, j, for_solver=True)
+        except operators.NotFusable as exc:
+            raise NotImplementedError("device-resident factors: %s -- it is applied between launches on a host copy here (fused in pgm / FISTA "
+                                      "without line search and user callables only)" % exc)
+        except NotImplementedError:
+            pass
+        raise NotImplementedError("device-resident factors with a user-defined prox for block %d (%r): the callable takes host arrays" % (j, h))
 
 
 def _host_pair(dev, buf, dt):
@@ -82,7 +106,7 @@ def _open_device(Y, A, S, W, f64=False, f64_mfma=False):
     reference does for fp64 inputs (nmf.py:39-41)."""
     if f64:
         try:                            # (a weighted likelihood: the matrix-core kernels whatever the shape -- the small-problem ones take no weights)
-            dev = DeviceNMF(A.shape[0], S.shape[1], A.shape[1], mode="f64" if (W is None and not f64_mfma) else "f64mfma", device=getattr(Y, "device", 0) if isinstance(Y, DeviceArrayRef) else 0)
+            dev = DeviceNMF(A.shape[0], S.shape[1], A.shape[1], mode="f64" if (W is None and not f64_mfma) else "f64mfma", device=device_of(Y, A))
         except NotImplementedError:     # the library's own test (pmx_ctx_create) is the authority: compute in fp32 and cast back, as for any other fp64 call
             dev = None
         if dev is not None:
@@ -94,13 +118,14 @@ def _open_device(Y, A, S, W, f64=False, f64_mfma=False):
     if isinstance(Y, DeviceArrayRef) and Y.dtype == np.float64:
         raise NotImplementedError("a float64 device-resident Y is taken by the fp64 kernels only (library operators and step rules, no "
                                   "Barzilai-Borwein / user callables, K <= 128); hand this call a float32 array")
+    refuse_f64_factors(A, S)            # (they could only be rounded into the caller's own arrays: the rule of a float64 device Y)
     _warn_f64_in_f32(Y, A, S)
     if Y is None:                       # a user `grad`: nothing M x N on the device (engine.DeviceNMF.set_host_grad)
         dev = DeviceNMF(A.shape[0], S.shape[1], A.shape[1], mode="f32")
         dev.set_host_grad(True)
         dev.set_factors(A, S)
         return dev
-    dev = open_weighted(A.shape[0], S.shape[1], A.shape[1], W, device=getattr(Y, "device", 0) if isinstance(Y, DeviceArrayRef) else 0)
+    dev = open_weighted(A.shape[0], S.shape[1], A.shape[1], W, device=device_of(Y, A))
     dev.set_Y(Y)
     dev.set_factors(A, S)
     return dev
@@ -145,6 +170,9 @@ def _e_rel_pair(e_rel):
 
 
 def _write_back(dev, A, S):
+    if isinstance(A, DeviceFactorRef):   # the caller's arrays live in HBM: device to device, S^T transposed by the kernel
+        dev.write_factors(A, S)
+        return
     dA, dS = dev.get_factors()
     A[...] = dA
     S[...] = dS
@@ -157,14 +185,15 @@ def _wants_iterates(callback):
 def _iterate(dev, A, S, max_iter, callback, advance, stop_iteration=True):
     """The host loop of every route that is not one fused call: the callback on the pre-update iterate (algorithms.py:90,
     :368, :802), ONE iteration through `advance(it) -> Result`, the factors written back, stop when the device says so.
-    A StopIteration from the callback ends pgm and adaprox quietly; bsdmm has no handler (stop_iteration=False) and its
+    The callback gets the caller's own objects (device-resident factors: refreshed device to device).  A StopIteration from the callback ends pgm and adaprox quietly; bsdmm has no handler (stop_iteration=False) and its
     caller gets the exception itself -- which is why this is a plain function: a generator would hand it on as
     RuntimeError (PEP 479).  -> the last Result (None: no iteration ran)."""
     res = None
+    cbA, cbS = factor_owner(A), factor_owner(S)
     for it in range(max_iter):
         if _wants_iterates(callback):
             try:
-                callback(A, S, it=it)
+                callback(cbA, cbS, it=it)
             except StopIteration:
                 if stop_iteration:
                     break
@@ -355,6 +384,7 @@ def pgm(X, grad, step, prox=None, accelerated=False, backtracking=False, f=None,
         raise TypeError("step must be callable")
     # prox_unity* along a factor's long axis: on the device (one more launch per application) when nothing else needs the host
     fused_long = _fuse_long_axis(seqs, host_prox, long_axis, host_route=user_step is not None or user_grad or bool(backtracking))
+    _refuse_host_callables(A, user_step, enumerate(host_prox))
     slow = user_step is not None or any(h is not None for h in host_prox) or user_grad
     # a user `step` next to the line search: the callable on the host once per iteration, the Beck-Teboulle loop on the device
     bt_user_step = backtracking and user_step is not None and not any(h is not None for h in host_prox) and not user_grad
@@ -480,6 +510,7 @@ def adaprox(X, grad, step, prox=None, scheme="adam", b1=0.9, b2=0.999, eps=1e-8,
         user_step = step
         _warn_host_path("step (%r)" % (step,))
     user_grad = Y is None
+    _refuse_host_callables(A, user_step, enumerate(host_prox))
     slow = user_step is not None or any(h is not None for h in host_prox) or user_grad
 
     Xs = (A, S)
@@ -615,6 +646,8 @@ def _bsdmm_nmf(X, grad, prox, proxs_g=None, steps_g=None, Ls=None, update_order=
     if closures is not None:
         _warn_host_path("proxs_f / steps_f_cb (%r, %r)" % closures)
         Xt = utils._as_tuple(X)
+        if any(as_device_factor(x) is not None for x in Xt):
+            raise NotImplementedError("device-resident factors with generic proxs_f / steps_f_cb closures: the callables take host arrays")
         if (len(Xt) != 2 or np.ndim(Xt[0]) != 2 or np.ndim(Xt[1]) != 2 or np.shape(Xt[0])[1] != np.shape(Xt[1])[0]):
             raise NotImplementedError("bsdmm with generic proxs_f / steps_f_cb closures runs on the device only for a two-block problem "
                                       "X = [A (M x K), S (K x N)] (got blocks of shapes %s); other block structures are outside the "
@@ -648,7 +681,7 @@ def _bsdmm_nmf(X, grad, prox, proxs_g=None, steps_g=None, Ls=None, update_order=
             # (n_order = 0 means "default order" to the C ABI, so this case never reaches the device.)
             if _wants_iterates(callback):
                 for it in range(max_iter):
-                    callback(A, S, it=it)
+                    callback(factor_owner(A), factor_owner(S), it=it)
             logger.info("Completed {0} iterations".format(max_iter))
             logger.warning("Solution did not converge")
             return [None, None]
@@ -674,6 +707,7 @@ def _bsdmm_nmf(X, grad, prox, proxs_g=None, steps_g=None, Ls=None, update_order=
         pairs = [_member(q, j, "proxs_g member") for q in g]
         seq_g.append([sq for sq, _ in pairs])
         host_g.append([h for _, h in pairs])
+    _refuse_host_callables(A, None, list(enumerate(host_f)) + [(j, h) for j, hs in enumerate(host_g) for h in hs])
     slow = any(h is not None for h in host_f) or any(h is not None for hs in host_g for h in hs) or closures is not None
 
     # [r4] fp64 inputs of a small problem: fp64 arithmetic on the device (k_small_f64.hip: k64_bsdmm_block), as the reference's own

@@ -35,6 +35,7 @@
 #include "k_small_f64.hip"
 #include "k_grad_f64.hip"
 #include "k_big_f64.hip"
+#include "k_xfer.hip"
 
 // ------------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -988,6 +989,75 @@ extern "C" int pmx_download_f64(pmx_ctx* c, int buf, double* host, int64_t count
     if (rc != PMX_OK) return rc;
     if (count != n) FAIL(PMX_E_INVALID, "buffer %d holds %lld doubles, got %lld", buf, (long long)n, (long long)count);
     HIP_CHECK(hipMemcpyAsync(host, d, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    return PMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// factors that already live in HBM: one block between the caller's view and a context buffer (k_xfer.hip)
+// ------------------------------------------------------------------------------------------------
+// the block (0: M x K, 1: S^T's N x K) that pmx_upload addresses with this buffer id
+static int buf_block(int buf) {
+    if (buf >= PMX_BUF_Z0 && buf < PMX_BUF_TG0 + 2 * PMX_MAX_G) return ((buf - PMX_BUF_Z0) % (2 * PMX_MAX_G)) / PMX_MAX_G;
+    return buf & 1;
+}
+
+// argument checks of both directions -> the context's array and the caller's strides along its rows (sr) and components (sk)
+static int xfer_lookup(pmx_ctx* c, int buf, const void* dptr, int64_t stride0, int64_t stride1, int is_f64, bool writable, void** ctx_arr,
+                       int64_t* rows, int64_t* sr, int64_t* sk) {
+    if (!c || !dptr) FAIL(PMX_E_INVALID, "NULL argument");
+    if ((is_f64 != 0) != c->f64) FAIL(PMX_E_UNSUPPORTED, "the array's element type (%s) is not the context's (%s)", is_f64 ? "float64" : "float32", c->f64 ? "float64" : "float32");
+    HIP_CHECK(hipSetDevice(c->device));
+    int64_t n;
+    if (c->f64) {
+        double* d;
+        int rc = buf_lookup_f64(c, buf, writable, &d, &n);
+        if (rc != PMX_OK) return rc;
+        *ctx_arr = d;
+    } else {
+        float** slot;
+        int rc = buf_lookup(c, buf, &slot, &n, writable);
+        if (rc != PMX_OK) return rc;
+        *ctx_arr = *slot;
+    }
+    const int j = buf_block(buf);
+    *rows = c->rows[j];
+    // block 0 is M x K in the caller's orientation, block 1 K x N
+    *sr = j == 0 ? stride0 : stride1;
+    *sk = j == 0 ? stride1 : stride0;
+    const int64_t K = c->K;
+    const bool copy = *sk == 1 && (*sr >= K || *rows == 1), transpose = *sr == 1 && (*sk >= *rows || K == 1);
+    if (!copy && !transpose)
+        FAIL(PMX_E_INVALID, "strides (%lld, %lld) of a %lld x %lld block: one of them must be 1 and the other at least the extent it steps over",
+             (long long)stride0, (long long)stride1, (long long)(j == 0 ? *rows : K), (long long)(j == 0 ? K : *rows));
+    if ((*rows + XFER_TILE - 1) / XFER_TILE * ((K + XFER_TILE - 1) / XFER_TILE) > 0x7fffffffLL || (*rows * K + XFER_THREADS - 1) / XFER_THREADS > 0x7fffffffLL)
+        FAIL(PMX_E_UNSUPPORTED, "block too large for one launch");
+    return PMX_OK;
+}
+
+extern "C" int pmx_factor_from_device(pmx_ctx* c, int buf, const void* dptr, int64_t stride0, int64_t stride1, int is_f64) {
+    if (c) { c->absmax_by_finish = false; c->gram_by_update = false; c->bt_grad_fresh = false; }
+    void* arr; int64_t rows, sr, sk;
+    int rc = xfer_lookup(c, buf, dptr, stride0, stride1, is_f64, true, &arr, &rows, &sr, &sk);
+    if (rc != PMX_OK) return rc;
+    // The array interface that hands `dptr` over carries no stream, and the context's stream does not wait for the legacy one
+    // (hipStreamNonBlocking): everything the caller enqueued on ANY stream of this device before the call is finished first.
+    HIP_CHECK(hipDeviceSynchronize());
+    if (c->f64) launch_xfer<double>((double*)arr, (double*)const_cast<void*>(dptr), rows, c->K, sr, sk, false, c->stream);
+    else launch_xfer<float>((float*)arr, (float*)const_cast<void*>(dptr), rows, c->K, sr, sk, false, c->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(c->stream));       // (the caller may change its array as soon as the call returns)
+    return PMX_OK;
+}
+
+extern "C" int pmx_factor_to_device(pmx_ctx* c, int buf, void* dptr, int64_t stride0, int64_t stride1, int is_f64) {
+    void* arr; int64_t rows, sr, sk;
+    int rc = xfer_lookup(c, buf, dptr, stride0, stride1, is_f64, false, &arr, &rows, &sr, &sk);
+    if (rc != PMX_OK) return rc;
+    if (c->f64) launch_xfer<double>((double*)arr, (double*)dptr, rows, c->K, sr, sk, true, c->stream);
+    else launch_xfer<float>((float*)arr, (float*)dptr, rows, c->K, sr, sk, true, c->stream);
+    HIP_CHECK(hipGetLastError());
+    // the caller's streams are not ordered against the context's: the data is in place when the call returns
     HIP_CHECK(hipStreamSynchronize(c->stream));
     return PMX_OK;
 }

@@ -126,6 +126,110 @@ def as_device_array(obj):
     return DeviceArrayRef(obj)
 
 
+class DeviceFactorRef:
+    """A factor (A: M x K, S: K x N) that is ALREADY in HBM and is updated there, in place: anything that speaks
+    `__cuda_array_interface__`, writable, two-dimensional, float32 or float64, row- or column-major with any pitch (one of the two
+    strides is the unit stride; the stride of an axis of extent 1 does not count).  Unlike Y it is not adopted by the kernels: the
+    context keeps its own copies (S as S^T) and moves the block device to device at entry, at exit and before every callback
+    (include/pmx.h: pmx_factor_from_device / pmx_factor_to_device; csrc/k_xfer.hip).  `strides` are in ELEMENTS, `dtype` is the NumPy
+    dtype the solvers compute their return values in, `owner` the caller's object."""
+
+    def __init__(self, obj):
+        cai = obj.__cuda_array_interface__
+        ts = cai.get("typestr")
+        if ts not in ("<f4", "=f4", "|f4", "<f8", "=f8", "|f8"):
+            raise TypeError("a device-resident factor must be float32 or float64 (got %r)" % (ts,))
+        es = 8 if ts.endswith("8") else 4
+        shape = tuple(int(v) for v in cai["shape"])
+        if len(shape) != 2:
+            raise TypeError("a device-resident factor must be two-dimensional (got shape %r)" % (shape,))
+        data = cai["data"]
+        if bool(data[1]):
+            raise TypeError("a device-resident factor is updated in place: a read-only array cannot be one")
+        strides = cai.get("strides")
+        if strides is None:
+            st = (shape[1], 1)
+        else:
+            if len(strides) != 2 or any(int(s) % es for s in strides):
+                raise TypeError("a device-resident factor's strides %r are not whole elements" % (tuple(strides),))
+            st = tuple(int(s) // es for s in strides)
+        # one unit stride, the other axis stepping over at least that axis's extent (an axis of extent 1 is never stepped along)
+        rowmajor = (st[1] == 1 or shape[1] == 1) and (st[0] >= shape[1] or shape[0] == 1)
+        colmajor = (st[0] == 1 or shape[0] == 1) and (st[1] >= shape[0] or shape[1] == 1)
+        if not (rowmajor or colmajor):
+            if 1 not in st:
+                raise TypeError("a device-resident factor needs unit stride along one of its axes (element strides %r)" % (st,))
+            raise TypeError("a device-resident factor's rows overlap (shape %r, element strides %r)" % (shape, st))
+        if rowmajor:
+            st = (st[0] if shape[0] > 1 else max(shape[1], 1), 1)
+        else:
+            st = (1, st[1] if shape[1] > 1 else max(shape[0], 1))
+        self.ptr, self.shape, self.strides, self.owner = int(data[0]), shape, st, obj
+        self.dtype = np.dtype(np.float64 if es == 8 else np.float32)
+        self.ndim = 2
+        self.device = _device_index(obj)
+
+    def __array__(self, *a, **k):
+        raise TypeError("this array lives on the GPU; proxmin_amd updates it in place")
+
+
+def _device_index(obj):
+    """the HIP device an array lives on: obj.device.index (torch), obj.device.id (CuPy) or an int"""
+    dev = getattr(obj, "device", None)
+    for v in (getattr(dev, "index", None), getattr(dev, "id", None), dev):
+        if isinstance(v, (int, np.integer)) and not isinstance(v, bool):
+            return int(v)
+    raise TypeError("cannot tell which GPU this device-resident factor lives on (no .device.index, .device.id or integer .device)")
+
+
+def as_device_factor(obj):
+    """DeviceFactorRef for a factor that lives on the GPU, None for host data"""
+    if isinstance(obj, DeviceFactorRef):
+        return obj
+    if isinstance(obj, np.ndarray) or not hasattr(obj, "__cuda_array_interface__"):
+        return None
+    if getattr(obj, "is_cuda", True) is False:       # a torch tensor on the host
+        return None
+    return DeviceFactorRef(obj)
+
+
+def factor_pair(A, S):
+    """-> (A, S) as they are for host factors, (DeviceFactorRef, DeviceFactorRef) for factors in HBM; one of each is refused"""
+    rA, rS = as_device_factor(A), as_device_factor(S)
+    if (rA is None) != (rS is None):
+        raise TypeError("A and S must both be host arrays or both live on the GPU (A is %s, S is %s)"
+                        % tuple("on the device" if r is not None else "on the host" for r in (rA, rS)))
+    if rA is None:
+        return A, S
+    if rA.device != rS.device:
+        raise ValueError("A lives on GPU %d and S on GPU %d" % (rA.device, rS.device))
+    return rA, rS
+
+
+def factor_owner(X):
+    """what the caller passed: the callback's argument"""
+    return X.owner if isinstance(X, DeviceFactorRef) else X
+
+
+def device_of(Y, A, default=0):
+    """The GPU a call runs on: where its device-resident arrays are (Y and the factors must agree), else `default`."""
+    dY = Y.device if isinstance(Y, DeviceArrayRef) else None
+    dA = A.device if isinstance(A, DeviceFactorRef) else None
+    if dY is not None and dA is not None and dY != dA:
+        raise ValueError("Y lives on GPU %d and the factors on GPU %d" % (dY, dA))
+    return dA if dA is not None else (dY if dY is not None else default)
+
+
+_F64_FACTORS_IN_F32 = ("float64 device-resident factors are taken by the fp64 kernels only (float64 Y, library operators and step rules, no "
+                       "Barzilai-Borwein, K <= 128); this call computes in float32: hand it float32 arrays")
+
+
+def refuse_f64_factors(*X):
+    """float64 factors in HBM on a call that computes in fp32 (they could only be rounded into the caller's own array)"""
+    if any(isinstance(x, DeviceFactorRef) and x.dtype == np.float64 for x in X):
+        raise NotImplementedError(_F64_FACTORS_IN_F32)
+
+
 class DeviceNMF:
     """Device state for one factorisation problem Y (M x N) ~ A (M x K) @ S (K x N)."""
 
@@ -141,7 +245,7 @@ class DeviceNMF:
         _lib.check(self.lib.pmx_ctx_create(C.byref(h), device, self.M, self.N, self.K, mode_id,
                                            C.c_void_p(stream) if stream else None))
         self.h = h
-        self._keep = []
+        self._keep, self._kept_for = [], {}
         # a split-precision context that fell off its fast kernel says so once (pmx_k1_info knows): ragged shapes and
         # K outside {64, 128} run the generic split-bf16 kernels or the exact-fp32 one, 1.5-3 x slower per pass
         if mode not in ("f32", "f64", "f64mfma"):
@@ -257,7 +361,38 @@ class DeviceNMF:
         _lib.check(self.lib.pmx_download(self.h, buf, _vp(out), out.size))
         return out
 
+    def _check_ref(self, ref, j):
+        want = (self.M, self.K) if j == 0 else (self.K, self.N)
+        assert ref.shape == want, "A must be M x K and S K x N"
+        if ref.device != self.device:
+            raise ValueError("the array lives on GPU %d, this context on GPU %d" % (ref.device, self.device))
+        if (ref.dtype == np.float64) != self.f64:
+            raise NotImplementedError(_F64_FACTORS_IN_F32 if not self.f64 else "an fp64 context takes float64 device-resident factors")
+
+    def _from_device(self, buf, ref, j=None):
+        """block j (default `buf & 1`) from the caller's array in HBM, device to device (include/pmx.h: pmx_factor_from_device: it waits for
+        everything the caller enqueued on the device before the call)"""
+        self._check_ref(ref, buf & 1 if j is None else j)
+        old = self._kept_for.get(buf)            # one owner per buffer: a context that serves many calls (nmf._factors_only) lets go of the last one
+        if old is not None:
+            self._keep[:] = [o for o in self._keep if o is not old]
+        self._kept_for[buf] = ref.owner
+        self._keep.append(ref.owner)
+        _lib.check(self.lib.pmx_factor_from_device(self.h, buf, C.c_void_p(ref.ptr), ref.strides[0], ref.strides[1], int(self.f64)))
+
+    def _to_device(self, buf, ref, j=None):
+        """block j (default `buf & 1`) into the caller's array in HBM: its logical elements only, complete when the call returns"""
+        self._check_ref(ref, buf & 1 if j is None else j)
+        _lib.check(self.lib.pmx_factor_to_device(self.h, buf, C.c_void_p(ref.ptr), ref.strides[0], ref.strides[1], int(self.f64)))
+
     def set_factors(self, A, S):
+        if isinstance(A, DeviceFactorRef) or isinstance(S, DeviceFactorRef):
+            A, S = factor_pair(A, S)
+            self._check_ref(A, 0)                      # (both checked before either is copied)
+            self._check_ref(S, 1)
+            self._from_device(_lib.BUF_A, A)
+            self._from_device(_lib.BUF_ST, S)
+            return
         assert A.shape == (self.M, self.K) and S.shape == (self.K, self.N), "A must be M x K and S K x N"
         self._upload(_lib.BUF_A, A)
         self._upload(_lib.BUF_ST, np.asarray(S).T)
@@ -265,8 +400,18 @@ class DeviceNMF:
     def get_factors(self):
         return self._download(_lib.BUF_A, self.M), self._download(_lib.BUF_ST, self.N).T
 
+    def write_factors(self, A, S):
+        """the current factors into the caller's device-resident arrays (DeviceFactorRef), device to device"""
+        self._check_ref(A, 0)
+        self._check_ref(S, 1)
+        self._to_device(_lib.BUF_A, A)
+        self._to_device(_lib.BUF_ST, S)
+
     def put(self, base, j, arr):
         """upload block j (0: M x K array, 1: K x N array) of a two-block state (moments, Z/U, ...)."""
+        if isinstance(arr, DeviceFactorRef):
+            self._from_device(base + j, arr, j)
+            return
         self._upload(base + j, arr if j == 0 else np.asarray(arr).T)
 
     def get(self, base, j):

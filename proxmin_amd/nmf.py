@@ -20,7 +20,7 @@ from functools import partial
 import numpy as np
 
 from . import algorithms, operators
-from .engine import DeviceNMF, open_weighted, as_device_array, DeviceArrayRef
+from .engine import DeviceNMF, open_weighted, as_device_array, DeviceArrayRef, DeviceFactorRef, factor_pair, device_of, refuse_f64_factors
 
 logger = logging.getLogger("proxmin")
 
@@ -44,11 +44,19 @@ def _shape_of(Y):
     return ref.shape if ref is not None else np.shape(Y)
 
 
+def _factors(A, S):
+    """(A, S) as NumPy arrays, or as engine.DeviceFactorRef when both live in HBM (one of each: TypeError)"""
+    A, S = factor_pair(A, S)
+    if isinstance(A, DeviceFactorRef):
+        return A, S
+    return np.asarray(A), np.asarray(S)
+
+
 def _device_for(A, S, Y, W=None):
     """Context with Y (and W) and the factors on the device (weights: engine.open_weighted picks the kernel)."""
-    A, S = np.asarray(A), np.asarray(S)
+    A, S = _factors(A, S)                        # host arrays, or factors that live in HBM (engine.DeviceFactorRef)
     Y = as_device_array(Y) or np.asarray(Y)      # a Y that lives in HBM is adopted in place (engine.DeviceArrayRef)
-    device = getattr(Y, "device", 0) if isinstance(Y, DeviceArrayRef) else 0
+    device = device_of(Y, A)
     # [r6] float64 arrays: the fp64 kernels, like the reference's own arithmetic (nmf.py:39-41)
     from .engine import f64_applies
     if all(x.dtype == np.float64 for x in (Y, A, S)) and f64_applies(Y.shape[0], Y.shape[1], A.shape[1], weighted=W is not None):
@@ -64,6 +72,7 @@ def _device_for(A, S, Y, W=None):
             return dev
     if isinstance(Y, DeviceArrayRef) and Y.dtype == np.float64:
         raise NotImplementedError("a float64 device-resident Y goes with float64 factors (the fp64 kernels, K <= 128)")
+    refuse_f64_factors(A, S)
     dev = open_weighted(Y.shape[0], Y.shape[1], A.shape[1], W, device=device)
     dev.set_Y(Y)
     dev.set_factors(A, S)
@@ -108,11 +117,13 @@ def _factors_only(A, S, f64_ok=False):
     result is a function of (A, S) alone -- pmx_step_pgm restarts its power iteration on a context without a solver.  [r6] The cache is
     guarded by a lock held for the whole call (the reference's step_pgm is a pure, thread-safe function), keyed by the device
     (PMX_DEVICE, default 0) as well, and closed by an atexit hook."""
-    A, S = np.asarray(A), np.asarray(S)
-    device = int(os.environ.get("PMX_DEVICE", "0"))
+    A, S = _factors(A, S)
+    device = device_of(None, A, default=int(os.environ.get("PMX_DEVICE", "0")))      # factors in HBM: the GPU they live on
     # [r6] float64 factors: lambda_max from fp64 Gram matrices (the reference calls LAPACK on float64 arrays, utils.py:14-35)
     from .engine import f64_applies
     mode = "f64" if (f64_ok and A.dtype == np.float64 and S.dtype == np.float64 and f64_applies(A.shape[0], S.shape[1], A.shape[1])) else "f32"
+    if mode == "f32":
+        refuse_f64_factors(A, S)
     key = (device, A.shape[0], S.shape[1], A.shape[1], mode)
     _FACTOR_LOCK.acquire()
     try:
@@ -140,6 +151,9 @@ def grad_likelihood(*X, Y=0, W=1):
     """(D S^T, A^T D) with D = W (A S - Y) (nmf.py:28-41): one launch of the fused residual-gradient
     kernel.  Returns arrays in the dtype of A."""
     A, S = X
+    if isinstance(factor_pair(A, S)[0], DeviceFactorRef):
+        raise NotImplementedError("nmf.grad_likelihood returns arrays: device-resident factors are not taken here (the solvers do: "
+                                  "nmf(), algorithms.pgm / adaprox / bsdmm)")
     with _device_for(A, S, Y, _weights(W, _shape_of(Y))) as dev:
         gA, gS = dev.grad()
     dt = np.asarray(A).dtype
@@ -174,7 +188,7 @@ def step_adaprox(*X, it=None):
     A, S = X
     with _factors_only(A, S) as dev:
         aA, aS = dev.step_adaprox()
-    dt = np.asarray(A).dtype
+    dt = _factors(A, S)[0].dtype
     return aA.astype(dt), aS.astype(dt)[:, None]
 
 
@@ -292,7 +306,13 @@ def nmf(
     (converged, M, V, Vhat); bsdmm: converged).  `algorithm` must be one of THIS package's
     `algorithms.pgm / adaprox / bsdmm` (identity test, nmf.py:141).
 
-    Beyond the reference: Y may already live in HBM (anything with `__cuda_array_interface__`, float32: adopted in place); and with
+    Beyond the reference: Y may already live in HBM (anything with `__cuda_array_interface__`, float32: adopted in place); so may A and
+    S -- both or neither; a torch tensor on the GPU, a CuPy array; float32 or float64, row- or column-major with any pitch -- which are then
+    read and updated where they are, device to device (engine.DeviceFactorRef), and a `callback` is handed the caller's own objects.  Such
+    a call stays on the device: library operators and step rules only (a user prox / step / grad takes host arrays and raises
+    NotImplementedError, as do float64 device factors on a call that computes in float32); W, warm-start moments and all return values are
+    host NumPy arrays in the factors' dtype.  Work enqueued on the arrays on any stream before the call is waited for; do not touch them
+    while the call runs.  And with
     `M_global=<rows of the whole problem>` (plus optional `group=`, `comm=`, `s_split=`) the arrays are one rank's rows of a row-sharded
     run over a torch.distributed process group (see _nmf_sharded).
     """
@@ -302,6 +322,8 @@ def nmf(
     # and A (S is replicated) and the call runs on the process group `group` (default: the world) with one packed collective per
     # iteration (proxmin_amd/distributed.py).  Without M_global the call is the reference's: one process, one GPU.
     if "M_global" in algorithm_args:
+        if isinstance(factor_pair(A, S)[0], DeviceFactorRef):
+            raise NotImplementedError("row-sharded nmf() (M_global=) takes host factors: device-resident A / S are not carried by the sharded drivers")
         return _nmf_sharded(Y, A, S, W, prox_A, prox_S, algorithm, step, max_iter, e_rel, callback, dict(algorithm_args))
 
     grad = partial(grad_likelihood, Y=Y, W=W)
