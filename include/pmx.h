@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PMX_ABI_VERSION 6
+#define PMX_ABI_VERSION 7
 
 /* ---- status codes -------------------------------------------------------------------- */
 enum {
@@ -81,7 +81,7 @@ enum {
                             small problem; tests) */
 };
 
-/* ---- proximal operators: proxmin/operators.py:20-160 ---------------------------------- */
+/* ---- proximal operators: proxmin/operators.py:20-184 ---------------------------------- */
 enum {
     PMX_PROX_NONE = -1,      /* prox=None: adaprox skips the sub-iteration loop (algorithms.py:380) */
     PMX_PROX_ID = 0,         /* prox_id          operators.py:20  */
@@ -94,7 +94,8 @@ enum {
     PMX_PROX_HARD = 7,       /* prox_hard        operators.py:109 */
     PMX_PROX_HARD_PLUS = 8,  /* prox_hard_plus   operators.py:127 */
     PMX_PROX_SOFT = 9,       /* prox_soft        operators.py:138 */
-    PMX_PROX_SOFT_PLUS = 10  /* prox_soft_plus   operators.py:153 */
+    PMX_PROX_SOFT_PLUS = 10, /* prox_soft_plus   operators.py:153 */
+    PMX_PROX_MAX_ENTROPY = 11 /* prox_max_entropy operators.py:163-184  [ABI v7]  (gamma in pmx_prox.thresh; solved in the log domain) */
 };
 
 /* One proximal operator.  `unit` says which sum prox_unity* normalises by, in DEVICE layout:
@@ -109,7 +110,11 @@ typedef struct pmx_prox {
     int32_t op;
     int32_t unit;
     double thresh;      /* [ABI v3] fp64 (was float): the fp64 contexts threshold with the caller's own value -- 0.01f differs from
-                           0.01 by 2e-8 relative; the fp32 kernels use (float)thresh exactly as before */
+                           0.01 by 2e-8 relative; the fp32 kernels use (float)thresh exactly as before.
+                           [ABI v7] PMX_PROX_MAX_ENTROPY: gamma (operators.py:163); gamma_ = gamma * step with relative = 1.  Only
+                           entries > 0 change; where gamma_ is <= 0 or NaN they become NaN.  With per-component or per-element
+                           steps gamma_ is formed element by element.  Finite for every finite entry > 0, also where the
+                           reference's exp() overflows */
     int32_t relative;
     int32_t reserved;   /* 0 */
 } pmx_prox;

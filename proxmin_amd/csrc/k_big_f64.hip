@@ -135,7 +135,7 @@ void launch_gram64(const Gram64Args& a, int KP, hipStream_t s) {
 // pgm / FISTA update (algorithms.py:93-108,130-135): grid (nbx, 2), nbx <= EW_BLOCKS; the partial-sum slots of idle workgroups stay zero.
 // nbx decides how the rows -- and with them the partial sums of the stopping test -- are dealt to workgroups: a small context
 // (K <= 16, M, N <= 8192) launches one half-wave per row of the longer factor, everything else EW_BLOCKS workgroups.
-template <int NC>
+template <int NC, bool ME = false>
 __global__ __launch_bounds__(EW_THREADS) void k64b_pgm_update(Pgm64Args a) {
     __shared__ double scratch[2 * EW_WAVES];
     const int j = blockIdx.y;
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(EW_THREADS) void k64b_pgm_update(Pgm64Args a) {
             const double xe = a.accelerated ? (ok[c] ? a.Xe[j][e] : 0.0) : xo[c];
             v[c] = xe - s * g[c];                                            // algorithms.py:107-108
         }
-        prox_row<double, NC>(v, ok, a.prox[j], sk);
+        prox_row<double, NC, 32, ME>(v, ok, a.prox[j], sk);
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             if (!ok[c]) continue;
@@ -176,8 +176,15 @@ __global__ __launch_bounds__(EW_THREADS) void k64b_pgm_update(Pgm64Args a) {
     double red[2] = {d2, n2};
     block_sum_store<2>(red, part_ptr(a.partials, SL_DIFF2, j) + blockIdx.x, (int64_t)2 * EW_BLOCKS, scratch);
 }
+// (every launch wrapper below with a `true` branch: the instances that hold prox_max_entropy, for a sequence that names it)
 void launch_pgm64b_update(const Pgm64Args& a, int nbx, hipStream_t s) {
     const dim3 grid(nbx, 2), block(EW_THREADS);
+    if (seq_has_me(a.prox[0]) || seq_has_me(a.prox[1])) {
+        if (a.K <= 32) hipLaunchKernelGGL((k64b_pgm_update<1, true>), grid, block, 0, s, a);
+        else if (a.K <= 64) hipLaunchKernelGGL((k64b_pgm_update<2, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k64b_pgm_update<4, true>), grid, block, 0, s, a);
+        return;
+    }
     if (a.K <= 32) hipLaunchKernelGGL(k64b_pgm_update<1>, grid, block, 0, s, a);
     else if (a.K <= 64) hipLaunchKernelGGL(k64b_pgm_update<2>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(k64b_pgm_update<4>, grid, block, 0, s, a);
@@ -213,7 +220,7 @@ struct Bt64Args {
     int do_block[2];
     double* partials;
 };
-template <int NC>
+template <int NC, bool ME = false>
 __global__ __launch_bounds__(EW_THREADS) void k64b_bt_update(Bt64Args a) {
     __shared__ double scratch[3 * EW_WAVES];
     __shared__ double smax[2][EW_WAVES];
@@ -237,7 +244,7 @@ __global__ __launch_bounds__(EW_THREADS) void k64b_bt_update(Bt64Args a) {
             xp[c] = ok[c] ? a.Xp[j][e] : 0.0;
             v[c] = (ok[c] ? a.E[j][e] : 0.0) - ts * g[c];
         }
-        prox_row<double, NC>(v, ok, a.prox[j], sk);
+        prox_row<double, NC, 32, ME>(v, ok, a.prox[j], sk);
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             if (!ok[c]) continue;
@@ -276,6 +283,12 @@ __global__ __launch_bounds__(256) void k64b_bt_finish(BtFin64Args a) {
 }
 void launch_bt64_update(const Bt64Args& a, hipStream_t s) {
     const dim3 grid(EW_BLOCKS, 2), block(EW_THREADS);
+    if (seq_has_me(a.prox[0]) || seq_has_me(a.prox[1])) {
+        if (a.K <= 32) hipLaunchKernelGGL((k64b_bt_update<1, true>), grid, block, 0, s, a);
+        else if (a.K <= 64) hipLaunchKernelGGL((k64b_bt_update<2, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k64b_bt_update<4, true>), grid, block, 0, s, a);
+        return;
+    }
     if (a.K <= 32) hipLaunchKernelGGL(k64b_bt_update<1>, grid, block, 0, s, a);
     else if (a.K <= 64) hipLaunchKernelGGL(k64b_bt_update<2>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(k64b_bt_update<4>, grid, block, 0, s, a);
@@ -286,7 +299,7 @@ void launch_bt64_finish(const BtFin64Args& a, hipStream_t s) { hipLaunchKernelGG
 // bSDMM block update (algorithms.py:805-844, utils.py:269-391; identity L) over the grid; its sums go to the reduction slots
 // k_bsdmm_decide folds (SL_DIFF2, SL_NORM2, SL_G0 + 4 i ..)
 // ------------------------------------------------------------------------------------------------
-template <int NC>
+template <int NC, bool ME = false>
 __global__ __launch_bounds__(EW_THREADS) void k64b_bsdmm_update(Bsdmm64Args a, double* partials) {
     __shared__ double scratch[4 * PMX_MAX_G * EW_WAVES];
     DevStatus* st = a.status;
@@ -304,13 +317,19 @@ __global__ __launch_bounds__(EW_THREADS) void k64b_bsdmm_update(Bsdmm64Args a, d
 #pragma unroll
     for (int i = 0; i < 4 * PMX_MAX_G; ++i) redg[i] = 0.0;
     const int64_t hw = ((int64_t)blockIdx.x * EW_THREADS + threadIdx.x) >> 5, nhw = ((int64_t)gridDim.x * EW_THREADS) >> 5;
-    for (int64_t r = hw; r < a.rows; r += nhw) bsdmm64_row<NC, 32>(a, r, l32, ok, sf, sg, w, nisg, red, redg);
+    for (int64_t r = hw; r < a.rows; r += nhw) bsdmm64_row<NC, 32, ME>(a, r, l32, ok, sf, sg, w, nisg, red, redg);
     block_sum_store<2>(red, part_ptr(partials, SL_DIFF2, j) + blockIdx.x, (int64_t)2 * EW_BLOCKS, scratch);
     __syncthreads();
     block_sum_store<4 * PMX_MAX_G>(redg, part_ptr(partials, SL_G0, j) + blockIdx.x, (int64_t)2 * EW_BLOCKS, scratch);
 }
 void launch_bsdmm64b_update(const Bsdmm64Args& a, double* partials, hipStream_t s) {
     const dim3 grid(EW_BLOCKS), block(EW_THREADS);
+    if (bsdmm64_has_me(a)) {
+        if (a.K <= 32) hipLaunchKernelGGL((k64b_bsdmm_update<1, true>), grid, block, 0, s, a, partials);
+        else if (a.K <= 64) hipLaunchKernelGGL((k64b_bsdmm_update<2, true>), grid, block, 0, s, a, partials);
+        else hipLaunchKernelGGL((k64b_bsdmm_update<4, true>), grid, block, 0, s, a, partials);
+        return;
+    }
     if (a.K <= 32) hipLaunchKernelGGL(k64b_bsdmm_update<1>, grid, block, 0, s, a, partials);
     else if (a.K <= 64) hipLaunchKernelGGL(k64b_bsdmm_update<2>, grid, block, 0, s, a, partials);
     else hipLaunchKernelGGL(k64b_bsdmm_update<4>, grid, block, 0, s, a, partials);
@@ -405,7 +424,7 @@ __global__ __launch_bounds__(EW_THREADS) void k64b_ada_moment(Ada64bArgs b) {
     }
 }
 // one proximal pass (algorithms.py:386-392) of each block whose loop is still running; grid (EW_BLOCKS, 2)
-template <int NC>
+template <int NC, bool ME = false>
 __global__ __launch_bounds__(EW_THREADS) void k64b_ada_sub(Ada64bArgs b) {
     __shared__ double scratch[2 * EW_WAVES];
     const Ada64Args& a = b.a;
@@ -446,7 +465,7 @@ __global__ __launch_bounds__(EW_THREADS) void k64b_ada_sub(Ada64bArgs b) {
             const double x = ok[c] ? a.X[j][e] : 0.0, ps = ok[c] ? a.Psi[j][e] : 0.0;
             v[c] = zz[c] - rat[c] * ps * (zz[c] - x);
         }
-        prox_row<double, NC>(v, ok, a.prox[j], gamma);
+        prox_row<double, NC, 32, ME>(v, ok, a.prox[j], gamma);
 #pragma unroll
         for (int c = 0; c < NC; ++c)
             if (ok[c]) {
@@ -555,7 +574,16 @@ void launch_ada64b_head(const Ada64bArgs& b, hipStream_t s) {        // step siz
     hipLaunchKernelGGL(k64b_alpha, dim3(1), dim3(256), 0, s, b);
     PMX_ADA64B(k64b_ada_moment, grid2, b);
 }
-void launch_ada64b_sub(const Ada64bArgs& b, hipStream_t s) { const dim3 grid2(EW_BLOCKS, 2); PMX_ADA64B(k64b_ada_sub, grid2, b); }
+void launch_ada64b_sub(const Ada64bArgs& b, hipStream_t s) {
+    const dim3 grid2(EW_BLOCKS, 2);
+    if (seq_has_me(b.a.prox[0]) || seq_has_me(b.a.prox[1])) {
+        if (b.a.K <= 32) hipLaunchKernelGGL((k64b_ada_sub<1, true>), grid2, dim3(EW_THREADS), 0, s, b);
+        else if (b.a.K <= 64) hipLaunchKernelGGL((k64b_ada_sub<2, true>), grid2, dim3(EW_THREADS), 0, s, b);
+        else hipLaunchKernelGGL((k64b_ada_sub<4, true>), grid2, dim3(EW_THREADS), 0, s, b);
+        return;
+    }
+    PMX_ADA64B(k64b_ada_sub, grid2, b);
+}
 void launch_ada64b_close(const Ada64bArgs& b, hipStream_t s) {       // verdict, X <- z, outer test
     const dim3 grid2(EW_BLOCKS, 2);
     PMX_ADA64B(k64b_ada_finish, grid2, b);

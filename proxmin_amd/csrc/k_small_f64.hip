@@ -316,7 +316,7 @@ __device__ __forceinline__ void wg_sum(double (&v)[NV], double* sm /* >= NV * EW
     }
 }
 // G lanes per row (8 / 16 / 32 for K <= 8 / 16 / ..): 1024 / G rows per trip of the loops
-template <int G>
+template <int G, bool ME = false>
 __global__ __launch_bounds__(EW_THREADS) void k64_ada_iter(Ada64Args a) {
     constexpr int NG = EW_THREADS / G;       // row groups of the workgroup
     __shared__ double sm[2 * EW_WAVES];
@@ -378,7 +378,7 @@ __global__ __launch_bounds__(EW_THREADS) void k64_ada_iter(Ada64Args a) {
                     const int64_t e = r * K + l32;
                     const double zz = ok ? a.z[j][e] : 0.0, x = ok ? X[e] : 0.0, ps = ok ? a.Psi[j][e] : 0.0;
                     double v[1] = {zz - rat * ps * (zz - x)};
-                    prox_row<double, 1, G>(v, ok1, a.prox[j], gam1);
+                    prox_row<double, 1, G, ME>(v, ok1, a.prox[j], gam1);
                     if (ok) {
                         const double d = v[0] - zz;
                         red[0] += d * d;
@@ -431,6 +431,11 @@ __global__ __launch_bounds__(EW_THREADS) void k64_ada_iter(Ada64Args a) {
     }
 }
 void launch_ada64_iter(const Ada64Args& a, hipStream_t s) {
+    if (seq_has_me(a.prox[0]) || seq_has_me(a.prox[1])) {      // the instances that hold prox_max_entropy
+        if (a.K <= 8) hipLaunchKernelGGL((k64_ada_iter<8, true>), dim3(1), dim3(EW_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((k64_ada_iter<16, true>), dim3(1), dim3(EW_THREADS), 0, s, a);
+        return;
+    }
     if (a.K <= 8) hipLaunchKernelGGL(k64_ada_iter<8>, dim3(1), dim3(EW_THREADS), 0, s, a);
     else hipLaunchKernelGGL(k64_ada_iter<16>, dim3(1), dim3(EW_THREADS), 0, s, a);
 }
@@ -457,7 +462,7 @@ struct Bsdmm64Args {
 // one row of a block update: value c of lane l (of the G that share row r) is component l + G c.  dX, X = prox_f(..), then Z_i / U_i
 // of every constraint; the 2 + 4 n_g sums of the residual norms go to red2 / redg.  k64_bsdmm_block: NC = 1, G lanes per row;
 // k64b_bsdmm_update (k_big_f64.hip): NC values per lane, G = 32.
-template <int NC, int G>
+template <int NC, int G, bool ME = false>
 __device__ __forceinline__ void bsdmm64_row(const Bsdmm64Args& a, int64_t r, int l, const bool (&ok)[NC], double sf, double sg, double w, double nisg,
                                             double (&red2)[2], double (&redg)[4 * PMX_MAX_G]) {
     const int K = a.K;
@@ -475,7 +480,7 @@ __device__ __forceinline__ void bsdmm64_row(const Bsdmm64Args& a, int64_t r, int
             if (ok[c]) dx += w * (xo[c] - a.Z[i][e] + a.U[i][e]);
         v[c] = (xo[c] - dx) - sf * g[c];                        // utils.py:338 + nmf.py:185
     }
-    prox_row<double, NC, G>(v, ok, a.prox_f, skf);
+    prox_row<double, NC, G, ME>(v, ok, a.prox_f, skf);
 #pragma unroll
     for (int c = 0; c < NC; ++c)
         if (ok[c]) {
@@ -493,7 +498,7 @@ __device__ __forceinline__ void bsdmm64_row(const Bsdmm64Args& a, int64_t r, int
             uo[c] = ok[c] ? a.U[i][e] : 0.0;
             zn[c] = v[c] + uo[c];
         }
-        prox_row<double, NC, G>(zn, ok, a.prox_g[i], skg);
+        prox_row<double, NC, G, ME>(zn, ok, a.prox_g[i], skg);
 #pragma unroll
         for (int c = 0; c < NC; ++c)
             if (ok[c]) {
@@ -508,7 +513,7 @@ __device__ __forceinline__ void bsdmm64_row(const Bsdmm64Args& a, int64_t r, int
             }
     }
 }
-template <int G>
+template <int G, bool ME = false>
 __global__ __launch_bounds__(EW_THREADS) void k64_bsdmm_block(Bsdmm64Args a) {
     constexpr int NG = EW_THREADS / G;
     __shared__ double sm[4 * PMX_MAX_G * EW_WAVES];
@@ -526,7 +531,7 @@ __global__ __launch_bounds__(EW_THREADS) void k64_bsdmm_block(Bsdmm64Args a) {
 #pragma unroll
     for (int i = 0; i < 4 * PMX_MAX_G; ++i) redg[i] = 0.0;
     for (int64_t r = hw; r < a.rows; r += NG)                  // (whole half-waves take or skip a row: prox_unity* sums over its lanes)
-        bsdmm64_row<1, G>(a, r, l32, ok1, sf, sg, w, nisg, red, redg);
+        bsdmm64_row<1, G, ME>(a, r, l32, ok1, sf, sg, w, nisg, red, redg);
     wg_sum<2>(red, sm);
     wg_sum<4 * PMX_MAX_G>(redg, sm);
     if (tid == 0) {     // check_constraint_convergence (utils.py:349-391) and end-of-iteration bookkeeping
@@ -558,7 +563,17 @@ __global__ __launch_bounds__(EW_THREADS) void k64_bsdmm_block(Bsdmm64Args a) {
         }
     }
 }
+static bool bsdmm64_has_me(const Bsdmm64Args& a) {
+    bool me = seq_has_me(a.prox_f);
+    for (int i = 0; i < a.n_g && i < PMX_MAX_G; ++i) me = me || seq_has_me(a.prox_g[i]);
+    return me;
+}
 void launch_bsdmm64_block(const Bsdmm64Args& a, hipStream_t s) {
+    if (bsdmm64_has_me(a)) {
+        if (a.K <= 8) hipLaunchKernelGGL((k64_bsdmm_block<8, true>), dim3(1), dim3(EW_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((k64_bsdmm_block<16, true>), dim3(1), dim3(EW_THREADS), 0, s, a);
+        return;
+    }
     if (a.K <= 8) hipLaunchKernelGGL(k64_bsdmm_block<8>, dim3(1), dim3(EW_THREADS), 0, s, a);
     else hipLaunchKernelGGL(k64_bsdmm_block<16>, dim3(1), dim3(EW_THREADS), 0, s, a);
 }

@@ -3,7 +3,7 @@
 //   - gradient-slab folding, PGM / FISTA update           (proxmin/algorithms.py:93-108,130-135)
 //   - adaprox moment schemes, update, proximal sub-iterations (algorithms.py:147-245, :369-410)
 //   - block-SDMM primal/dual update and residual norms     (proxmin/utils.py:295-391)
-//   - the proximal operators themselves                    (proxmin/operators.py:20-160)
+//   - the proximal operators themselves                    (proxmin/operators.py:20-184)
 //
 // Both blocks are tall row-major matrices with K components per row (A: M x K, St = S^T: N x K), so
 // one set of kernels serves both.  A row is handled by LPR = 32 lanes (half a wavefront), lane l owning
@@ -205,14 +205,74 @@ __device__ __forceinline__ double fold_partials_nanmax_wt(const double* part) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// proximal operators on one row held across G lanes          (proxmin/operators.py:20-160)
+// proximal operators on one row held across G lanes          (proxmin/operators.py:20-184)
 // The ONE implementation: T = float (NC values per lane, G = 32) for the fp32 kernels, T = double for k_big_f64.hip (the same
 // layout) and k_small_f64.hip (NC = 1, G = 8 / 16 / 32 lanes per row).
 // v[c] is component l + G c of the row; ok[c] says whether that component exists (< K).
 // sk[c] is the step the solver passes for that component (scalar steps: all equal).
 // ------------------------------------------------------------------------------------------------
-template <class T, int NC, int G = 32>
+//
+// prox_max_entropy (operators.py:163-184): y = gamma_ W(exp(x / gamma_ - 1) / gamma_) for x > 0, the minimiser of
+// gamma_ y ln y + (y - x)^2 / 2.  Solved in the log domain, where nothing overflows: y = gamma_ w with
+//     w + ln w = L,   L = x / gamma_ - 1 - ln gamma_.
+// Start (at most 6 % off, the worst at L = 2 and at L -> 1 from below):
+//     L >= 1   w = L - ln L + ln L / L                        (the first terms of W's expansion at infinity)
+//     L <  1   w = e (60 + 114 e + 17 e^2) / (60 + 174 e + 101 e^2),  e = exp(L)         (W's [3/2] Pade approximant at 0)
+// then Newton on w + ln w - L, w <- w (1 + L - ln w) / (1 + w), whose relative error goes r -> r^2 / (2 (1 + w)):
+// 6e-2, 1.8e-3, 1.6e-6, 1.3e-12, 8e-25.  float is converged after 3 steps and double after 4; both run one more, which moves the
+// result by no more than the rounding of a step itself (L - ln w cancels where L is very negative: |L| eps; over L in [-45, 2000]
+// and gamma_ in [1e-3, 1e4] at most 0.32 of the bound 8 eps (1 + (|x / gamma_| + |ln gamma_| + 1) / (1 + w)) the tests hold the
+// result to).  The count is fixed: the lanes of a row stay together for the row_sum operators of a sequence.
+// Below L = ME_LMIN (float -20, double -40) w = exp(L) to the type's precision (w = e - e^2 + ..), so y = exp(x / gamma_ - 1)
+// without forming the w that would underflow; where x / gamma_ is beyond 1e30 / 1e300 y = x to the type's precision.
+// gamma_ <= 0 or NaN: NaN (the reference writes NaN at 0 and numbers without meaning below).
+template <class T> __device__ __forceinline__ T me_log(T x);
+template <> __device__ __forceinline__ float me_log<float>(float x) { return logf(x); }
+template <> __device__ __forceinline__ double me_log<double>(double x) { return log(x); }
+template <class T> __device__ __forceinline__ T me_exp(T x);
+template <> __device__ __forceinline__ float me_exp<float>(float x) { return expf(x); }
+template <> __device__ __forceinline__ double me_exp<double>(double x) { return exp(x); }
+template <class T>
+__device__ __forceinline__ T max_entropy_one(T x, T g) {
+    constexpr bool F32 = sizeof(T) == 4;
+    constexpr T LMIN = F32 ? (T)-20 : (T)-40;
+    constexpr T QMAX = F32 ? (T)1e30 : (T)1e300;
+    constexpr int STEPS = F32 ? 4 : 5;
+    const T q = x / g;
+    const T Lraw = q - (T)1 - me_log<T>(g);
+    const T L = Lraw > LMIN ? Lraw : LMIN;                 // (a NaN L runs the iteration at LMIN; the selects below decide)
+    T w;
+    if (L >= (T)1) {
+        const T l = me_log<T>(L);
+        w = L - l + l / L;
+    } else {
+        const T e = me_exp<T>(L);
+        w = e * (((T)17 * e + (T)114) * e + (T)60) / (((T)101 * e + (T)174) * e + (T)60);
+    }
+#pragma unroll
+    for (int i = 0; i < STEPS; ++i) w = w * (((T)1 + L - me_log<T>(w)) / ((T)1 + w));
+    T y = g * w;
+    if (!(Lraw > LMIN)) y = me_exp<T>(q - (T)1);
+    if (!(q < QMAX)) y = x;
+    if (!(g > (T)0)) y = (T)NAN;
+    return y;
+}
+
+// ME: the instantiation holds prox_max_entropy.  Kernels are instantiated without it as well -- those instances are what they
+// were before the operator existed -- and the launch wrappers pick the instance with it only for a sequence that names it.
+template <class T, int NC, int G = 32, bool ME = false>
 __device__ __forceinline__ void prox_one(T (&v)[NC], const bool (&ok)[NC], const pmx_prox& p, const T (&sk)[NC]) {
+    if constexpr (ME) {
+        if (p.op == PMX_PROX_MAX_ENTROPY) {                         // only entries > 0 change (operators.py:178-183)
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const T th = (T)p.thresh;                           // gamma
+                const T y = max_entropy_one<T>(v[c], p.relative ? th * sk[c] : th);
+                v[c] = v[c] > (T)0 ? y : v[c];
+            }
+            return;
+        }
+    }
     switch (p.op) {
         case PMX_PROX_ID: break;
         case PMX_PROX_ZERO:
@@ -264,10 +324,16 @@ __device__ __forceinline__ void prox_one(T (&v)[NC], const bool (&ok)[NC], const
     }
 }
 
-template <class T, int NC, int G = 32>
+template <class T, int NC, int G = 32, bool ME = false>
 __device__ __forceinline__ void prox_row(T (&v)[NC], const bool (&ok)[NC], const ProxSeq& ps, const T (&sk)[NC]) {
     for (int r = 0; r < ps.repeat; ++r)
-        for (int q = 0; q < ps.n; ++q) prox_one<T, NC, G>(v, ok, ps.seq[q], sk);
+        for (int q = 0; q < ps.n; ++q) prox_one<T, NC, G, ME>(v, ok, ps.seq[q], sk);
+}
+// (host) does a sequence name prox_max_entropy?  The launch wrappers' switch between a kernel's two instances.
+static inline bool seq_has_me(const ProxSeq& ps) {
+    for (int q = 0; q < ps.n && q < PMX_MAX_SEQ; ++q)
+        if (ps.seq[q].op == PMX_PROX_MAX_ENTROPY) return true;
+    return false;
 }
 
 // row iteration: half-wave h of the grid handles rows h, h + H, h + 2H, ...
@@ -394,7 +460,7 @@ struct ProxArgs {
     ProxSeq prox;
     float stepk[MAXK];
 };
-template <int NC>
+template <int NC, bool ME = false>
 __global__ __launch_bounds__(EW_THREADS) void k_prox_apply(ProxArgs a) {
     const int K = a.K;
     ROW_LOOP_BEGIN(a.rows)
@@ -407,7 +473,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_prox_apply(ProxArgs a) {
             v[c] = ok[c] ? a.X[r * K + kk] : 0.f;
             sk[c] = ok[c] ? a.stepk[kk] : 0.f;
         }
-        prox_row(v, ok, a.prox, sk);
+        prox_row<float, NC, 32, ME>(v, ok, a.prox, sk);
 #pragma unroll
         for (int c = 0; c < NC; ++c)
             if (ok[c]) a.X[r * K + l32 + 32 * c] = v[c];
@@ -460,7 +526,7 @@ struct PgmArgs {
     float* gramPart;         // [2][GRAM_BLOCKS][KP*KP]
     int KP;
 };
-template <int NC>
+template <int NC, bool ME = false>
 __global__ __launch_bounds__(EW_THREADS) void k_pgm_update(PgmArgs a) {
     __shared__ double scratch[2 * EW_WAVES];
     __shared__ int s_last;
@@ -499,7 +565,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_pgm_update(PgmArgs a) {
                 if (ok[c]) a.T[j][r * K + l32 + 32 * c] = v[c];
             continue;
         }
-        if (mode == 0) prox_row(v, ok, px, sk);
+        if (mode == 0) prox_row<float, NC, 32, ME>(v, ok, px, sk);
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             if (ok[c]) {
@@ -596,7 +662,7 @@ struct BtArgs {
     int mode[2];
     float* Tb[2];
 };
-template <int NC>
+template <int NC, bool ME = false>
 __global__ __launch_bounds__(EW_THREADS) void k_bt_update(BtArgs a) {
     __shared__ double scratch[3 * EW_WAVES];
     if (chain_halted(a.status)) return;
@@ -631,7 +697,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_bt_update(BtArgs a) {
                 }
             continue;
         }
-        if (a.mode[j] == 0) prox_row(v, ok, a.prox[j], sk);
+        if (a.mode[j] == 0) prox_row<float, NC, 32, ME>(v, ok, a.prox[j], sk);
 #pragma unroll
         for (int c = 0; c < NC; ++c)
             if (ok[c]) {
@@ -1049,7 +1115,7 @@ struct PgmUnityArgs {
     PgmUnityBlock b[2];
     int finish;
 };
-template <int NC>
+template <int NC, bool ME = false>
 __global__ __launch_bounds__(EW_THREADS) void k_pgm_unity(PgmUnityArgs aa) {
     __shared__ double scratch[2 * EW_WAVES];
     __shared__ int s_last;
@@ -1103,7 +1169,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_pgm_unity(PgmUnityArgs aa) {
             if (ub.div && ok[c]) v[c] = v[c] / tot[l32 + 32 * c];
             sk[c] = s;
         }
-        for (int p = ub.p0; p < ub.p1; ++p) prox_one(v, ok, px.seq[p % px.n], sk);
+        for (int p = ub.p0; p < ub.p1; ++p) prox_one<float, NC, 32, ME>(v, ok, px.seq[p % px.n], sk);
         if (!finish) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
@@ -1414,7 +1480,7 @@ __device__ __forceinline__ void sub_steps(const SubArgs& a, int j, double* scrat
 // in one 32-lane group); per pass the two sums of the stopping test go to that pass's ring slot.  The launch writes
 // only the state after its LAST pass: if the loop turns out to have ended inside the launch, k_ada_finish replays
 // the few passes from the launch's (untouched) input.  Launch b reads X (b = 0) or zb[(b-1) & 1] and writes zb[b & 1].
-template <int NC, int NT>
+template <int NC, int NT, bool ME = false>
 __global__ __launch_bounds__(EW_THREADS) void k_ada_sub(SubArgs a) {
     __shared__ double scratch[2 * NT * EW_WAVES];
     if (chain_halted(a.status)) return;
@@ -1447,7 +1513,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_ada_sub(SubArgs a) {
             float v[NC];
 #pragma unroll
             for (int c = 0; c < NC; ++c) v[c] = z[c] - rat[c] * ps[c] * (z[c] - x[c]);
-            prox_row(v, ok, a.prox[j], gam);
+            prox_row<float, NC, 32, ME>(v, ok, a.prox[j], gam);
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 if (ok[c]) {
@@ -1481,7 +1547,7 @@ struct FinishArgs {
     float* absmax_out;   // [2][EW_BLOCKS] per-workgroup max |X_j| of the iterate written here (the fp16 K1's operand
                          // scales, saving its own k_absmax pass), or nullptr
 };
-template <int NC>
+template <int NC, bool ME = false>
 __global__ __launch_bounds__(EW_THREADS) void k_ada_finish(FinishArgs a) {
     __shared__ double scratch[2 * EW_WAVES];
     __shared__ float sm[(EW_THREADS / 32) * MAXK];
@@ -1545,7 +1611,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_ada_finish(FinishArgs a) {
                 float v[NC];
 #pragma unroll
                 for (int c = 0; c < NC; ++c) v[c] = z[c] - rat[c] * ps[c] * (z[c] - x[c]);
-                prox_row(v, ok, a.s.prox[j], gam);
+                prox_row<float, NC, 32, ME>(v, ok, a.s.prox[j], gam);
 #pragma unroll
                 for (int c = 0; c < NC; ++c) z[c] = v[c];
             }
@@ -2192,7 +2258,7 @@ struct BsdmmArgs {
     int KP;              //      gram_per(rows) <= BSDMM_GRAM_ROWS)
 };
 constexpr int BSDMM_GRAM_ROWS = 64;      // rows of X_j a workgroup keeps in LDS for its partial Gram matrix (factors of <= 16384 rows)
-template <int NC>
+template <int NC, bool ME = false>
 __global__ __launch_bounds__(EW_THREADS) void k_bsdmm_update(BsdmmArgs a) {
     __shared__ double scratch[EW_WAVES * (2 + 4 * PMX_MAX_G)];
     __shared__ __attribute__((aligned(16))) float gtile[NC <= 2 ? BSDMM_GRAM_ROWS : 1][NC <= 2 ? 32 * NC + 4 : 4];   // the workgroup's rows of the new X_j (gramPart)
@@ -2246,7 +2312,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_bsdmm_update(BsdmmArgs a) {
                     if (ok[c]) a.Tf[r * K + l32 + 32 * c] = v[c];
                 continue;
             }
-            if (!(a.stage == 2 && a.host_f)) prox_row(v, ok, a.prox_f, sk);
+            if (!(a.stage == 2 && a.host_f)) prox_row<float, NC, 32, ME>(v, ok, a.prox_f, sk);
 #pragma unroll
             for (int c = 0; c < NC; ++c)
                 if (ok[c]) {
@@ -2281,7 +2347,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_bsdmm_update(BsdmmArgs a) {
                 zn[c] = hosted ? (ok[c] ? a.T[i][e] : 0.f) : v[c] + uo[c];
                 sgk[c] = sg;
             }
-            if (!hosted) prox_row(zn, ok, a.prox_g[i], sgk);
+            if (!hosted) prox_row<float, NC, 32, ME>(zn, ok, a.prox_g[i], sgk);
 #pragma unroll
             for (int c = 0; c < NC; ++c)
                 if (ok[c]) {
@@ -2750,13 +2816,26 @@ __global__ __launch_bounds__(EW_THREADS) void k_shard_post_split(ShardPostSplitA
         else hipLaunchKernelGGL(KERNEL<4>, grid, dim3(EW_THREADS), 0, stream, args);              \
     } while (0)
 
+// the same for a kernel with an instance that holds prox_max_entropy: `me` picks it (seq_has_me of the launch's sequences)
+#define DISPATCH_NC_ME(K, me, KERNEL, grid, stream, args)                                                          \
+    do {                                                                                                           \
+        if (!(me)) DISPATCH_NC(K, KERNEL, grid, stream, args);                                                     \
+        else if ((K) <= 32) hipLaunchKernelGGL((KERNEL<1, true>), grid, dim3(EW_THREADS), 0, stream, args);         \
+        else if ((K) <= 64) hipLaunchKernelGGL((KERNEL<2, true>), grid, dim3(EW_THREADS), 0, stream, args);         \
+        else hipLaunchKernelGGL((KERNEL<4, true>), grid, dim3(EW_THREADS), 0, stream, args);                        \
+    } while (0)
+
 void launch_fold(const FoldArgs& a, int nblocks_y, hipStream_t s) { DISPATCH_NC(a.K, k_fold, dim3(EW_BLOCKS, nblocks_y), s, a); }
-void launch_prox_apply(const ProxArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_prox_apply, dim3(EW_BLOCKS), s, a); }
-void launch_pgm_update(const PgmArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_pgm_update, dim3(a.nbx > 0 ? a.nbx : EW_BLOCKS, 2), s, a); }
-void launch_pgm_unity(const PgmUnityArgs& a, hipStream_t s) { DISPATCH_NC(a.u.K, k_pgm_unity, dim3(a.u.nbx > 0 ? a.u.nbx : EW_BLOCKS, 2), s, a); }
+void launch_prox_apply(const ProxArgs& a, hipStream_t s) { DISPATCH_NC_ME(a.K, seq_has_me(a.prox), k_prox_apply, dim3(EW_BLOCKS), s, a); }
+void launch_pgm_update(const PgmArgs& a, hipStream_t s) {
+    DISPATCH_NC_ME(a.K, seq_has_me(a.prox[0]) || seq_has_me(a.prox[1]), k_pgm_update, dim3(a.nbx > 0 ? a.nbx : EW_BLOCKS, 2), s, a);
+}
+void launch_pgm_unity(const PgmUnityArgs& a, hipStream_t s) {
+    DISPATCH_NC_ME(a.u.K, seq_has_me(a.u.prox[0]) || seq_has_me(a.u.prox[1]), k_pgm_unity, dim3(a.u.nbx > 0 ? a.u.nbx : EW_BLOCKS, 2), s, a);
+}
 void launch_bb_reduce(const BBArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_bb_reduce, dim3(EW_BLOCKS, 2), s, a); }
 void launch_bb_step(const BBStepArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_bb_step, dim3(1), dim3(EW_THREADS), 0, s, a); }
-void launch_bt_update(const BtArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_bt_update, dim3(EW_BLOCKS, 2), s, a); }
+void launch_bt_update(const BtArgs& a, hipStream_t s) { DISPATCH_NC_ME(a.K, seq_has_me(a.prox[0]) || seq_has_me(a.prox[1]), k_bt_update, dim3(EW_BLOCKS, 2), s, a); }
 void launch_bt_collect(const BtCollectArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_bt_collect, dim3(1), dim3(EW_THREADS), 0, s, a); }
 void launch_bt_finish(const BtFinishArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_bt_finish, dim3(EW_BLOCKS, 2), dim3(EW_THREADS), 0, s, a); }
 void launch_pgm_decide(const DecideArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_pgm_decide, dim3(1), dim3(EW_THREADS), 0, s, a); }
@@ -2764,18 +2843,25 @@ void launch_colsum(const ColsumArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_cols
 void launch_alpha_init(const AlphaArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_alpha_init, dim3(1), dim3(EW_THREADS), 0, s, a); }
 void launch_colscale(const ColScaleArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_colscale, dim3(EW_BLOCKS), s, a); }
 void launch_ada_moment(const MomentArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_ada_moment, dim3(EW_BLOCKS, 2), s, a); }
-#define DISPATCH_NC_NT(K, NT, KERNEL, grid, stream, args)                                                          \
+#define DISPATCH_NC_NT(K, NT, ME, KERNEL, grid, stream, args)                                                      \
     do {                                                                                                           \
-        if ((K) <= 32) hipLaunchKernelGGL((KERNEL<1, NT>), grid, dim3(EW_THREADS), 0, stream, args);                \
-        else if ((K) <= 64) hipLaunchKernelGGL((KERNEL<2, NT>), grid, dim3(EW_THREADS), 0, stream, args);           \
-        else hipLaunchKernelGGL((KERNEL<4, NT>), grid, dim3(EW_THREADS), 0, stream, args);                          \
+        if ((K) <= 32) hipLaunchKernelGGL((KERNEL<1, NT, ME>), grid, dim3(EW_THREADS), 0, stream, args);            \
+        else if ((K) <= 64) hipLaunchKernelGGL((KERNEL<2, NT, ME>), grid, dim3(EW_THREADS), 0, stream, args);       \
+        else hipLaunchKernelGGL((KERNEL<4, NT, ME>), grid, dim3(EW_THREADS), 0, stream, args);                      \
     } while (0)
-void launch_ada_sub(const SubArgs& a, hipStream_t s) {
-    if (a.nt == 1) DISPATCH_NC_NT(a.K, 1, k_ada_sub, dim3(EW_BLOCKS, 2), s, a);
-    else if (a.nt == 4) DISPATCH_NC_NT(a.K, 4, k_ada_sub, dim3(EW_BLOCKS, 2), s, a);
-    else DISPATCH_NC_NT(a.K, SUB_NT_MAX, k_ada_sub, dim3(EW_BLOCKS, 2), s, a);
+template <bool ME>
+static void launch_ada_sub_t(const SubArgs& a, hipStream_t s) {
+    if (a.nt == 1) DISPATCH_NC_NT(a.K, 1, ME, k_ada_sub, dim3(EW_BLOCKS, 2), s, a);
+    else if (a.nt == 4) DISPATCH_NC_NT(a.K, 4, ME, k_ada_sub, dim3(EW_BLOCKS, 2), s, a);
+    else DISPATCH_NC_NT(a.K, SUB_NT_MAX, ME, k_ada_sub, dim3(EW_BLOCKS, 2), s, a);
 }
-void launch_ada_finish(const FinishArgs& a, hipStream_t s) { DISPATCH_NC(a.s.K, k_ada_finish, dim3(EW_BLOCKS, 2), s, a); }
+void launch_ada_sub(const SubArgs& a, hipStream_t s) {
+    if (seq_has_me(a.prox[0]) || seq_has_me(a.prox[1])) launch_ada_sub_t<true>(a, s);
+    else launch_ada_sub_t<false>(a, s);
+}
+void launch_ada_finish(const FinishArgs& a, hipStream_t s) {
+    DISPATCH_NC_ME(a.s.K, seq_has_me(a.s.prox[0]) || seq_has_me(a.s.prox[1]), k_ada_finish, dim3(EW_BLOCKS, 2), s, a);
+}
 void launch_ada_decide(const AdaDecideArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_ada_decide, dim3(1), dim3(EW_THREADS), 0, s, a); }
 // dynamic LDS of the fused tail: three state arrays of (slots[0] + slots[1]) x NC x 1024 floats
 static size_t ada_tail_lds_bytes(const TailArgs& a) {
@@ -2797,7 +2883,11 @@ hipError_t launch_ada_tail(const TailArgs& a, hipStream_t s) {
     if (a.m.K <= 64) return launch_ada_tail_t<2>(a, s);
     return launch_ada_tail_t<4>(a, s);
 }
-void launch_bsdmm_update(const BsdmmArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_bsdmm_update, dim3(EW_BLOCKS), s, a); }
+void launch_bsdmm_update(const BsdmmArgs& a, hipStream_t s) {
+    bool me = seq_has_me(a.prox_f);
+    for (int i = 0; i < a.n_g && i < PMX_MAX_G; ++i) me = me || seq_has_me(a.prox_g[i]);
+    DISPATCH_NC_ME(a.K, me, k_bsdmm_update, dim3(EW_BLOCKS), s, a);
+}
 void launch_shard_pack(const PackArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_shard_pack, dim3(EW_BLOCKS + PACK_XWG), s, a); }
 void launch_shard_gram_in(const GramInArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_shard_gram_in, dim3((a.n + 255) / 256), dim3(256), 0, s, a); }
 void launch_shard_post(const ShardPostArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_shard_post, dim3(1), dim3(EW_THREADS), 0, s, a); }

@@ -274,7 +274,8 @@ static bool prox_long_axis(const pmx_proxseq& p) {       // prox_unity* along th
         if ((p.seq[i].op == PMX_PROX_UNITY || p.seq[i].op == PMX_PROX_UNITY_PLUS) && p.seq[i].unit != 0) return true;
     return false;
 }
-// every operator is a coordinate-wise projection whose fixed point is reached in one pass (result independent of gamma)
+// every operator is a coordinate-wise projection whose fixed point is reached in one pass (result independent of gamma).
+// (A whitelist: prox_max_entropy, like relative prox_soft, is elementwise and step-dependent and is not one.)
 static bool seq_is_projection(const pmx_proxseq& p) {
     for (int i = 0; i < p.n; ++i) {
         const pmx_prox& q = p.seq[i];
@@ -286,11 +287,16 @@ static bool seq_is_projection(const pmx_proxseq& p) {
 }
 // long_axis_ok: the caller has a place for prox_unity* along the rows -- the stand-alone operator entry points (pmx_prox_apply /
 // pmx_prox_array) and pmx_pgm_begin (k_pgm_unity's chain)
+static bool prox_has_max_entropy(const pmx_proxseq& p) {
+    for (int i = 0; i < p.n && i < PMX_MAX_SEQ; ++i)
+        if (p.seq[i].op == PMX_PROX_MAX_ENTROPY) return true;
+    return false;
+}
 static int check_prox(const pmx_proxseq& p, const char* what, bool long_axis_ok = false) {
     if (p.n < 0 || p.n > PMX_MAX_SEQ) FAIL(PMX_E_INVALID, "%s: bad operator count %d", what, p.n);
     for (int i = 0; i < p.n; ++i) {
         const pmx_prox& q = p.seq[i];
-        if (q.op < PMX_PROX_ID || q.op > PMX_PROX_SOFT_PLUS) FAIL(PMX_E_INVALID, "%s: unknown prox op %d", what, q.op);
+        if (q.op < PMX_PROX_ID || q.op > PMX_PROX_MAX_ENTROPY) FAIL(PMX_E_INVALID, "%s: unknown prox op %d", what, q.op);
     }
     if (prox_long_axis(p) && !long_axis_ok)
         FAIL(PMX_E_UNSUPPORTED, "%s: prox_unity along the row dimension (numpy axis=0 on A / axis=1 on S) needs a grid-wide sum per "
@@ -2711,7 +2717,8 @@ extern "C" int pmx_adaprox_begin(pmx_ctx* c, const pmx_adaprox_params* p, int wa
     // resident (PMX_TAIL_FUSED=0: the four separate kernels; PMX_SUB_BATCH=1 implies them)
     c->tail_fused = false;
     if (!(getenv("PMX_TAIL_FUSED") && atoi(getenv("PMX_TAIL_FUSED")) == 0) && c->sub_nt != 1 && c->tailFaults == 0 &&
-        !p->host_prox[0] && !p->host_prox[1]) {
+        !p->host_prox[0] && !p->host_prox[1] &&
+        !prox_has_max_entropy(p->prox[0]) && !prox_has_max_entropy(p->prox[1])) {     // (k_ada_tail is built without prox_max_entropy: the four kernels hold it)
         int ncu = 0;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) ncu = 0;
         TailArgs probe{};

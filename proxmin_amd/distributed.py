@@ -460,7 +460,8 @@ def _device_tensor(ptr, n, device):
 
 def projection_type(seq):
     """True if every operator of a device sequence is a coordinate-wise projection whose result does not depend on the
-    proximal pass count (plus / id / zero / absolute min, max, hard): what S-split (and a sharded A) require."""
+    proximal pass count (plus / id / zero / absolute min, max, hard): what S-split (and a sharded A) require.
+    A whitelist: prox_soft* and prox_max_entropy (elementwise, but step-dependent) are not of this type."""
     box = {_lib.PROX[n] for n in ("id", "zero", "plus")}
     maybe = {_lib.PROX[n] for n in ("min", "max", "hard", "hard_plus") if n in _lib.PROX}
     return all(seq.seq[i].op in box or (seq.seq[i].op in maybe and not seq.seq[i].relative) for i in range(seq.n))

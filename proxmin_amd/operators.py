@@ -1,5 +1,5 @@
 """Proximal operators of the nmf() path -- same names, arguments and in-place behaviour as
-proxmin/operators.py:20-160 -- backed by the HIP operator kernel (csrc/k_update.hip, prox_one).
+proxmin/operators.py:20-184 -- backed by the HIP operator kernel (csrc/k_update.hip, prox_one).
 
 Two uses:
   * passed to `nmf.nmf()` as `prox_A` / `prox_S` / `proxs_g` (bare, or wrapped in
@@ -20,7 +20,7 @@ import numpy as np
 from . import _lib
 
 __all__ = ["prox_id", "prox_zero", "prox_plus", "prox_unity", "prox_unity_plus", "prox_min", "prox_max",
-           "prox_hard", "prox_hard_plus", "prox_soft", "prox_soft_plus", "AlternatingProjections"]
+           "prox_hard", "prox_hard_plus", "prox_soft", "prox_soft_plus", "prox_max_entropy", "AlternatingProjections"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -139,6 +139,30 @@ def prox_soft_plus(X, step, thresh=0, type="relative"):
     return _apply(X, step, "soft_plus", thresh=thresh, kind=type)
 
 
+def prox_max_entropy(X, step, gamma=1, type="relative"):
+    """Proximal operator of the entropy regulariser g(x) = gamma sum x ln x (operators.py:163-184), in place:
+    with gamma_ = gamma * step ("relative") or gamma ("absolute"), every entry x > 0 becomes the y > 0 with
+    y + gamma_ ln y = x - gamma_, i.e. gamma_ W(exp(x / gamma_ - 1) / gamma_) with the principal Lambert W.
+    Entries <= 0, NaN and -inf keep their value, +inf stays +inf (so the operator jumps at 0, as the reference's does).
+
+    Three differences from the reference, all of them where the reference has no usable answer:
+      * the equation is solved in the log domain, so the result is finite for every finite x > 0 -- the reference's
+        exp(x / gamma_ - 1) overflows to inf above 88.7 (float32 arrays) / 709 (float64);
+      * a per-component or per-element `step` with type="relative" (what adaprox passes; step arrays in pgm) applies
+        gamma * step element by element -- the broadcasting the reference intends and raises on (ValueError / TypeError);
+      * where gamma_ is <= 0 or NaN the entries > 0 become NaN (the reference writes NaN at 0 and numbers without
+        meaning below 0)."""
+    if isinstance(X, np.ndarray) and X.dtype != np.float32:
+        # computed in float32 like every operator called on an array; the entries the operator does not touch keep their own
+        # value (not its float32 rounding): "only entries > 0 change"
+        keep = ~(X > 0)
+        kept = X[keep]
+        _apply(X, step, "max_entropy", thresh=gamma, kind=type)
+        X[keep] = kept
+        return X
+    return _apply(X, step, "max_entropy", thresh=gamma, kind=type)
+
+
 class AlternatingProjections(object):
     """POCS composition of several operators (operators.py:187-224): the list is applied
     last-to-first, `repeat` times.  Inside nmf() a list of built-ins becomes one fused device
@@ -171,7 +195,7 @@ class AlternatingProjections(object):
 # ---------------------------------------------------------------------------------------------
 _BY_FUNC = {prox_id: "id", prox_zero: "zero", prox_plus: "plus", prox_unity: "unity", prox_unity_plus: "unity_plus",
             prox_min: "min", prox_max: "max", prox_hard: "hard", prox_hard_plus: "hard_plus",
-            prox_soft: "soft", prox_soft_plus: "soft_plus"}
+            prox_soft: "soft", prox_soft_plus: "soft_plus", prox_max_entropy: "max_entropy"}
 
 
 def _one_entry(prox, block):
@@ -192,7 +216,7 @@ def _one_entry(prox, block):
         return (op, unit, 0.0, 0)
     if op in ("id", "zero", "plus"):
         return None if kw else (op, 0, 0.0, 0)
-    thresh = kw.pop("thresh", 0)
+    thresh = kw.pop("gamma", 1) if op == "max_entropy" else kw.pop("thresh", 0)
     kind = kw.pop("type", "relative")
     if kw:
         return None
