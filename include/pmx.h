@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-#define PMX_ABI_VERSION 7
+#define PMX_ABI_VERSION 7 /* v7 grew, additively, by one op code (PMX_PROX_COMPONENTS) and two symbols (pmx_prox_table,
+                             pmx_prox_array_tables): no struct changed its layout, so the number stayed */
 
 /* ---- status codes -------------------------------------------------------------------- */
 enum {
@@ -95,7 +96,11 @@ enum {
     PMX_PROX_HARD_PLUS = 8,  /* prox_hard_plus   operators.py:127 */
     PMX_PROX_SOFT = 9,       /* prox_soft        operators.py:138 */
     PMX_PROX_SOFT_PLUS = 10, /* prox_soft_plus   operators.py:153 */
-    PMX_PROX_MAX_ENTROPY = 11 /* prox_max_entropy operators.py:163-184  [ABI v7]  (gamma in pmx_prox.thresh; solved in the log domain) */
+    PMX_PROX_MAX_ENTROPY = 11, /* prox_max_entropy operators.py:163-184  [ABI v7]  (gamma in pmx_prox.thresh; solved in the log domain) */
+    PMX_PROX_COMPONENTS = 12  /* [ABI v7] one operator PER COMPONENT: component k of every row gets row k of a table of K entries
+                                 (op, thresh, relative) set with pmx_prox_table -- prox_components (operators.py:87-103), and an
+                                 array `thresh` / `gamma` of the threshold operators (operators.py:4-14 broadcast per component:
+                                 a table whose rows share one op).  pmx_prox.reserved = 1 + the table's index, unit = 0 */
 };
 
 /* One proximal operator.  `unit` says which sum prox_unity* normalises by, in DEVICE layout:
@@ -116,11 +121,13 @@ typedef struct pmx_prox {
                            steps gamma_ is formed element by element.  Finite for every finite entry > 0, also where the
                            reference's exp() overflows */
     int32_t relative;
-    int32_t reserved;   /* 0 */
+    int32_t reserved;   /* 0; PMX_PROX_COMPONENTS: 1 + index of the entry's table (pmx_prox_table) */
 } pmx_prox;
 
 #define PMX_MAX_SEQ 4 /* AlternatingProjections of up to 4 built-ins (operators.py:187-211) */
 #define PMX_MAX_G 4   /* constraints per block for bsdmm                                      */
+#define PMX_MAX_TABLES 16 /* per-component tables of one context: one per entry of pgm's / adaprox's two sequences (8), and
+                             as many again for bsdmm's prox_f and proxs_g sequences */
 
 /* A (possibly composite) operator: seq[0..n-1] applied in the order stored, `repeat` times.
  * (The host wrapper reverses AlternatingProjections' list, which applies last-to-first.) */
@@ -283,6 +290,22 @@ int pmx_prox_apply(pmx_ctx* ctx, int buf, const pmx_proxseq* prox, const float* 
  * place): copies to the device, runs the operator kernel, copies back.  This is what calling
  * proxmin.operators.prox_* directly on an ndarray maps to. */
 int pmx_prox_array(int device, float* X, int64_t rows, int K, const pmx_proxseq* prox, const float* step_k);
+/* [ABI v7] Table `index` (0 .. PMX_MAX_TABLES - 1) of the context: K rows of the 24-byte pmx_prox, row k = the operator of
+ * component k (op, thresh, relative; unit = reserved = 0).  A row is an element-wise operator: id, zero, plus, min, max, hard,
+ * hard_plus, soft, soft_plus or max_entropy -- not prox_unity*, not PMX_PROX_COMPONENTS.  relative = 1 multiplies the row's
+ * threshold by the step of that component (operators.py:4-14), whatever kind of step the solver passes: a scalar, adaprox's
+ * per-component steps, pgm's per-element step arrays.  The fp32 kernels use (float)thresh, the fp64 kernels the double.
+ * This is prox_components (operators.py:87-103: component k gets prox[k]) along the axis that indexes the components.
+ * PMX_E_INVALID for K other than the context's, a row op outside that list or an index outside 0 .. PMX_MAX_TABLES - 1.
+ * The rows are copied to the device; call it BEFORE the *_begin / pmx_prox_apply whose sequences name the table (a sequence
+ * that names an index beyond PMX_MAX_TABLES answers PMX_E_UNSUPPORTED, one that names a table never set PMX_E_INVALID).
+ * (The row-sharded drivers of the Python package refuse such sequences: the sharded phases were not built for them.) */
+int pmx_prox_table(pmx_ctx* ctx, int index, const pmx_prox* rows, int K);
+/* [ABI v7] pmx_prox_array with per-component tables: `tables` holds ntables x K rows (table t at tables + t * K), and an
+ * entry PMX_PROX_COMPONENTS with reserved = 1 + t applies table t.  What calling an operator with an array `thresh`, or
+ * prox_components, directly on an ndarray maps to. */
+int pmx_prox_array_tables(int device, float* X, int64_t rows, int K, const pmx_proxseq* prox, const float* step_k,
+                          const pmx_prox* tables, int ntables);
 /* [ABI v4] context-free reductions of utils.BarzilaiBorweinStepper.step called as a FUNCTION on host arrays (utils.py:216-241; inside
  * pgm the rule runs fused, k_bb_reduce / k_bb_step): one block's X, G and the previous call's X_prev, G_prev (both NULL in the first
  * call: s = y = 0), `count` elements of float (is_f64 = 0) or double (1).  out = { sum s^2, sum s y, sum y^2, sum G^2, max|X|, max|G| }

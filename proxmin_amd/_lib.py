@@ -16,12 +16,13 @@ LIB_PATH = os.environ.get("PMX_LIB") or os.path.join(_HERE, "libpmx.so")   # PMX
 MAX_SEQ = 4
 MAX_G = 4
 MAXK = 128
+MAX_TABLES = 16                       # per-component operator tables of one context (PMX_MAX_TABLES)
 ABI_VERSION = 7
 
 # enums (include/pmx.h)
 MODE_F32, MODE_BF16X3, MODE_F16X2, MODE_F64, MODE_F16X2R, MODE_F64_MFMA = 0, 2, 3, 4, 5, 6
 PROX = {"id": 0, "zero": 1, "plus": 2, "unity": 3, "unity_plus": 4, "min": 5, "max": 6,
-        "hard": 7, "hard_plus": 8, "soft": 9, "soft_plus": 10, "max_entropy": 11}
+        "hard": 7, "hard_plus": 8, "soft": 9, "soft_plus": 10, "max_entropy": 11, "components": 12}
 SCHEME = {"adam": 0, "nadam": 1, "amsgrad": 2, "padam": 3, "adamx": 4, "radam": 5}
 BUF_A, BUF_ST, BUF_GA, BUF_GST, BUF_MA, BUF_MST, BUF_VA, BUF_VST, BUF_VHA, BUF_VHST = range(10)
 BUF_EVAL_A, BUF_EVAL_ST, BUF_TMP_A, BUF_TMP_ST, BUF_PSI_A, BUF_PSI_ST = 10, 11, 12, 13, 14, 15
@@ -93,6 +94,8 @@ _SIGNATURES = {
     "pmx_step_adaprox": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pmx_prox_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ProxSeq), C.c_void_p]),
     "pmx_prox_array": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.POINTER(ProxSeq), C.c_void_p]),
+    "pmx_prox_table": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Prox), C.c_int]),
+    "pmx_prox_array_tables": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.POINTER(ProxSeq), C.c_void_p, C.POINTER(Prox), C.c_int]),
     "pmx_bb_sums": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double)]),
     "pmx_pgm_begin": (C.c_int, [C.c_void_p, C.POINTER(PgmParams)]),
     "pmx_pgm_run": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Result)]),

@@ -385,6 +385,7 @@ def pgm(X, grad, step, prox=None, accelerated=False, backtracking=False, f=None,
     # prox_unity* along a factor's long axis: on the device (one more launch per application) when nothing else needs the host
     fused_long = _fuse_long_axis(seqs, host_prox, long_axis, host_route=user_step is not None or user_grad or bool(backtracking))
     _refuse_host_callables(A, user_step, enumerate(host_prox))
+    operators.check_tables(seqs, A.shape[1])
     slow = user_step is not None or any(h is not None for h in host_prox) or user_grad
     # a user `step` next to the line search: the callable on the host once per iteration, the Beck-Teboulle loop on the device
     bt_user_step = backtracking and user_step is not None and not any(h is not None for h in host_prox) and not user_grad
@@ -511,6 +512,7 @@ def adaprox(X, grad, step, prox=None, scheme="adam", b1=0.9, b2=0.999, eps=1e-8,
         _warn_host_path("step (%r)" % (step,))
     user_grad = Y is None
     _refuse_host_callables(A, user_step, enumerate(host_prox))
+    operators.check_tables(seqs, A.shape[1])
     slow = user_step is not None or any(h is not None for h in host_prox) or user_grad
 
     Xs = (A, S)
@@ -708,6 +710,7 @@ def _bsdmm_nmf(X, grad, prox, proxs_g=None, steps_g=None, Ls=None, update_order=
         seq_g.append([sq for sq, _ in pairs])
         host_g.append([h for _, h in pairs])
     _refuse_host_callables(A, None, list(enumerate(host_f)) + [(j, h) for j, hs in enumerate(host_g) for h in hs])
+    operators.check_tables(list(seq_f) + [q for g in seq_g for q in (g or [])], A.shape[1])
     slow = any(h is not None for h in host_f) or any(h is not None for hs in host_g for h in hs) or closures is not None
 
     # [r4] fp64 inputs of a small problem: fp64 arithmetic on the device (k_small_f64.hip: k64_bsdmm_block), as the reference's own

@@ -258,11 +258,54 @@ __device__ __forceinline__ T max_entropy_one(T x, T g) {
     return y;
 }
 
-// ME: the instantiation holds prox_max_entropy.  Kernels are instantiated without it as well -- those instances are what they
-// were before the operator existed -- and the launch wrappers pick the instance with it only for a sequence that names it.
+// one element-wise operator on one value, the operator chosen PER LANE (a row of a per-component table): the same expressions as
+// the uniform switch of prox_one below, so a table whose rows are equal gives the bits of the scalar operator
+template <class T>
+__device__ __forceinline__ T prox_elem(int op, T x, T t) {
+    switch (op) {
+        case PMX_PROX_ZERO: return (T)0;
+        case PMX_PROX_PLUS: return x < (T)0 ? (T)0 : x;
+        case PMX_PROX_MIN: return (x - t < (T)0) ? t : x;
+        case PMX_PROX_MAX: return (x - t > (T)0) ? t : x;
+        case PMX_PROX_HARD: return (fabs(x) < t) ? (T)0 : x;
+        case PMX_PROX_HARD_PLUS: x = (fabs(x) < t) ? (T)0 : x; return x < (T)0 ? (T)0 : x;
+        case PMX_PROX_SOFT:
+        case PMX_PROX_SOFT_PLUS: {
+            T m = fabs(x) - t;
+            m = m < (T)0 ? (T)0 : m;
+            const T sg = (T)(x > (T)0) - (T)(x < (T)0);
+            x = sg * m;
+            if (op == PMX_PROX_SOFT_PLUS) x = x < (T)0 ? (T)0 : x;
+            return x;
+        }
+        case PMX_PROX_MAX_ENTROPY: return x > (T)0 ? max_entropy_one<T>(x, t) : x;
+        default: return x;                                      // PMX_PROX_ID
+    }
+}
+
+// ME: the instantiation holds prox_max_entropy and the per-component tables (PMX_PROX_COMPONENTS).  Kernels are instantiated
+// without them as well -- those instances are what they were before these operators existed -- and the launch wrappers pick the
+// instance with them only for a sequence that names one (seq_has_me).
+// PMX_PROX_COMPONENTS: component k of the row takes row k of table p.reserved - 1 (tab: the tables' base, MAXK rows each;
+// include/pmx.h: pmx_prox_table).  A lane reads the rows of its own components only (`ok[c]`: nothing for a component that does
+// not exist) and applies them lane by lane: no cross-lane operation, so the lanes of a row stay together for a row_sum operator
+// elsewhere in the sequence.  The rows (at most 3 KiB per table, the same for every row of the factor) are read where they are
+// used and stay in the caches: holding them in registers across the row loop for up to PMX_MAX_SEQ entries would cost up to
+// 12 NC registers in kernels that sit at the occupancy edge already.
 template <class T, int NC, int G = 32, bool ME = false>
-__device__ __forceinline__ void prox_one(T (&v)[NC], const bool (&ok)[NC], const pmx_prox& p, const T (&sk)[NC]) {
+__device__ __forceinline__ void prox_one(T (&v)[NC], const bool (&ok)[NC], const pmx_prox& p, const T (&sk)[NC], const pmx_prox* tab = nullptr) {
     if constexpr (ME) {
+        if (p.op == PMX_PROX_COMPONENTS) {
+            const pmx_prox* rows = tab + (int64_t)(p.reserved - 1) * MAXK + (threadIdx.x & (G - 1));
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                if (!ok[c]) continue;
+                const pmx_prox q = rows[G * c];
+                const T th = (T)q.thresh;
+                v[c] = prox_elem<T>(q.op, v[c], q.relative ? th * sk[c] : th);
+            }
+            return;
+        }
         if (p.op == PMX_PROX_MAX_ENTROPY) {                         // only entries > 0 change (operators.py:178-183)
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
@@ -327,12 +370,12 @@ __device__ __forceinline__ void prox_one(T (&v)[NC], const bool (&ok)[NC], const
 template <class T, int NC, int G = 32, bool ME = false>
 __device__ __forceinline__ void prox_row(T (&v)[NC], const bool (&ok)[NC], const ProxSeq& ps, const T (&sk)[NC]) {
     for (int r = 0; r < ps.repeat; ++r)
-        for (int q = 0; q < ps.n; ++q) prox_one<T, NC, G, ME>(v, ok, ps.seq[q], sk);
+        for (int q = 0; q < ps.n; ++q) prox_one<T, NC, G, ME>(v, ok, ps.seq[q], sk, ps.tab);
 }
-// (host) does a sequence name prox_max_entropy?  The launch wrappers' switch between a kernel's two instances.
+// (host) does a sequence name prox_max_entropy or a per-component table?  The launch wrappers' switch between a kernel's two instances.
 static inline bool seq_has_me(const ProxSeq& ps) {
     for (int q = 0; q < ps.n && q < PMX_MAX_SEQ; ++q)
-        if (ps.seq[q].op == PMX_PROX_MAX_ENTROPY) return true;
+        if (ps.seq[q].op == PMX_PROX_MAX_ENTROPY || ps.seq[q].op == PMX_PROX_COMPONENTS) return true;
     return false;
 }
 
@@ -1169,7 +1212,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_pgm_unity(PgmUnityArgs aa) {
             if (ub.div && ok[c]) v[c] = v[c] / tot[l32 + 32 * c];
             sk[c] = s;
         }
-        for (int p = ub.p0; p < ub.p1; ++p) prox_one<float, NC, 32, ME>(v, ok, px.seq[p % px.n], sk);
+        for (int p = ub.p0; p < ub.p1; ++p) prox_one<float, NC, 32, ME>(v, ok, px.seq[p % px.n], sk, px.tab);
         if (!finish) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) {

@@ -245,6 +245,8 @@ struct pmx_ctx {
     bool ssplit = false;
     int64_t scol0 = 0, sncol = 0;
     float* comm_out = nullptr;             // caller-owned: this rank's chunk after the reduce-scatter
+    pmx_prox* tabs = nullptr;              // per-component operator tables (pmx_prox_table): [PMX_MAX_TABLES][MAXK] rows, allocated with the first
+    bool tab_set[PMX_MAX_TABLES] = {};
     float* stepArr[2] = {nullptr, nullptr};   // pgm, split iterations: per-element steps of a user `step` that returned arrays (PMX_BUF_STEP_*)
     int step_arr_mask = 0;                   // bit j: block j's step comes from stepArr[j] in the split phases that follow
     void* rccl_comm = nullptr;             // pmx_comm_init: an RCCL communicator of this context's device (collectives run on its stream)
@@ -262,11 +264,14 @@ static int dalloc(pmx_ctx* c, void** p, size_t bytes, bool zero = true) {
 template <class T>
 static int dallocT(pmx_ctx* c, T** p, size_t count, bool zero = true) { return dalloc(c, (void**)p, count * sizeof(T), zero); }
 
-static ProxSeq to_dev(const pmx_proxseq& p) {
+// the ONE place a kernel's operator sequence is built.  tab: base of the per-component tables its PMX_PROX_COMPONENTS entries
+// index (pmx_ctx::tabs; the temporary copy of pmx_prox_array_tables), nullptr for none
+static ProxSeq to_dev(const pmx_proxseq& p, const pmx_prox* tab) {
     ProxSeq d{};
     d.n = p.n;
     d.repeat = p.repeat < 1 ? 1 : p.repeat;
     for (int i = 0; i < PMX_MAX_SEQ; ++i) d.seq[i] = p.seq[i];
+    d.tab = tab;
     return d;
 }
 static bool prox_long_axis(const pmx_proxseq& p) {       // prox_unity* along the rows of the device array: a sum over the whole factor
@@ -287,16 +292,27 @@ static bool seq_is_projection(const pmx_proxseq& p) {
 }
 // long_axis_ok: the caller has a place for prox_unity* along the rows -- the stand-alone operator entry points (pmx_prox_apply /
 // pmx_prox_array) and pmx_pgm_begin (k_pgm_unity's chain)
-static bool prox_has_max_entropy(const pmx_proxseq& p) {
+static bool prox_has_max_entropy(const pmx_proxseq& p) {      // ... or a per-component table: the operators of the <.., true> instances
     for (int i = 0; i < p.n && i < PMX_MAX_SEQ; ++i)
-        if (p.seq[i].op == PMX_PROX_MAX_ENTROPY) return true;
+        if (p.seq[i].op == PMX_PROX_MAX_ENTROPY || p.seq[i].op == PMX_PROX_COMPONENTS) return true;
     return false;
 }
-static int check_prox(const pmx_proxseq& p, const char* what, bool long_axis_ok = false) {
+static bool row_op_ok(int op) {      // what a row of a per-component table may be: the element-wise operators
+    return op == PMX_PROX_ID || op == PMX_PROX_ZERO || op == PMX_PROX_PLUS || (op >= PMX_PROX_MIN && op <= PMX_PROX_MAX_ENTROPY);
+}
+// tab_set: which tables exist (pmx_ctx::tab_set), or nullptr with `ntables` of them (pmx_prox_array_tables; -1: the context has none)
+static int check_prox(const pmx_proxseq& p, const char* what, bool long_axis_ok = false, const bool* tab_set = nullptr, int ntables = -1) {
     if (p.n < 0 || p.n > PMX_MAX_SEQ) FAIL(PMX_E_INVALID, "%s: bad operator count %d", what, p.n);
     for (int i = 0; i < p.n; ++i) {
         const pmx_prox& q = p.seq[i];
-        if (q.op < PMX_PROX_ID || q.op > PMX_PROX_MAX_ENTROPY) FAIL(PMX_E_INVALID, "%s: unknown prox op %d", what, q.op);
+        if (q.op < PMX_PROX_ID || q.op > PMX_PROX_COMPONENTS) FAIL(PMX_E_INVALID, "%s: unknown prox op %d", what, q.op);
+        if (q.op != PMX_PROX_COMPONENTS) continue;
+        if (q.unit != 0) FAIL(PMX_E_INVALID, "%s: PMX_PROX_COMPONENTS works along the components of a row (unit 0)", what);
+        if (q.reserved < 1) FAIL(PMX_E_INVALID, "%s: PMX_PROX_COMPONENTS without a table (reserved = 1 + its index)", what);
+        if (tab_set != nullptr && q.reserved > PMX_MAX_TABLES)
+            FAIL(PMX_E_UNSUPPORTED, "%s: table %d of at most %d per-component tables", what, q.reserved - 1, PMX_MAX_TABLES);
+        if (tab_set != nullptr ? !tab_set[q.reserved - 1] : q.reserved > ntables)
+            FAIL(PMX_E_INVALID, "%s: PMX_PROX_COMPONENTS names table %d, which has not been set (pmx_prox_table)", what, q.reserved - 1);
     }
     if (prox_long_axis(p) && !long_axis_ok)
         FAIL(PMX_E_UNSUPPORTED, "%s: prox_unity along the row dimension (numpy axis=0 on A / axis=1 on S) needs a grid-wide sum per "
@@ -308,7 +324,8 @@ static int check_prox(const pmx_proxseq& p, const char* what, bool long_axis_ok 
 
 // one operator sequence on a rows x K device array, incl. prox_unity* along the rows (column sums over all rows).
 // `colpart` is scratch of EW_BLOCKS * MAXK doubles.
-static int apply_prox_standalone(float* X, int64_t rows, int K, const pmx_proxseq& prox, const float* step_k, double* colpart, hipStream_t stream) {
+static int apply_prox_standalone(float* X, int64_t rows, int K, const pmx_proxseq& prox, const float* step_k, double* colpart, hipStream_t stream,
+                                 const pmx_prox* tab = nullptr) {
     bool along_rows = false;
     for (int i = 0; i < prox.n; ++i)
         along_rows |= (prox.seq[i].op == PMX_PROX_UNITY || prox.seq[i].op == PMX_PROX_UNITY_PLUS) && prox.seq[i].unit != 0;
@@ -318,7 +335,7 @@ static int apply_prox_standalone(float* X, int64_t rows, int K, const pmx_proxse
     a.K = K;
     for (int k = 0; k < K; ++k) a.stepk[k] = step_k[k];
     if (!along_rows) {
-        a.prox = to_dev(prox);
+        a.prox = to_dev(prox, tab);
         launch_prox_apply(a, stream);
         return PMX_OK;
     }
@@ -329,13 +346,13 @@ static int apply_prox_standalone(float* X, int64_t rows, int K, const pmx_proxse
             one.n = 1; one.repeat = 1; one.seq[0] = prox.seq[i];
             const bool rows_unity = (one.seq[0].op == PMX_PROX_UNITY || one.seq[0].op == PMX_PROX_UNITY_PLUS) && one.seq[0].unit != 0;
             if (!rows_unity) {
-                a.prox = to_dev(one);
+                a.prox = to_dev(one, tab);
                 launch_prox_apply(a, stream);
                 continue;
             }
             if (one.seq[0].op == PMX_PROX_UNITY_PLUS) {           // plus first (operators.py:48-52)
                 one.seq[0].op = PMX_PROX_PLUS; one.seq[0].unit = 0;
-                a.prox = to_dev(one);
+                a.prox = to_dev(one, tab);
                 launch_prox_apply(a, stream);
             }
             ColsumArgs cs{};
@@ -1670,7 +1687,7 @@ static int pgm64_enqueue_iteration(pmx_ctx* c) {
         u.slab[j] = c->slabd[j];
         u.nslab[j] = j == 0 ? c->nSlabA : c->nSlabS;
         u.rows[j] = c->rows[j];
-        u.prox[j] = to_dev(p.prox[j]);
+        u.prox[j] = to_dev(p.prox[j], c->tabs);
     }
     u.K = (int)c->K;
     u.status = c->dstatus;
@@ -1717,7 +1734,7 @@ static int pgm64_bt_iteration(pmx_ctx* c) {
     for (int j = 0; j < 2; ++j) {
         u.X[j] = c->Xd[j]; u.E[j] = c->Xed[j]; u.Xp[j] = c->Xprevd[j]; u.G[j] = c->Gd[j];
         u.rows[j] = c->rows[j];
-        u.prox[j] = to_dev(p.prox[j]);
+        u.prox[j] = to_dev(p.prox[j], c->tabs);
         u.do_block[j] = 1;
     }
     u.K = (int)c->K;
@@ -1929,7 +1946,7 @@ static PgmArgs pgm_args(pmx_ctx* c, bool own_S = false) {
         u.G[j] = own_S ? s_view(c, j, c->G[j]) : c->G[j];
         u.slab[j] = slab_ref(c, j);
         u.rows[j] = own_S ? upd_rows(c, j) : c->rows[j];
-        u.prox[j] = to_dev(p.prox[j]);
+        u.prox[j] = to_dev(p.prox[j], c->tabs);
     }
     u.K = (int)c->K;
     u.status = c->dstatus;
@@ -2006,37 +2023,69 @@ extern "C" int pmx_prox_apply(pmx_ctx* c, int buf, const pmx_proxseq* prox, cons
     if (c) { c->absmax_by_finish = false; c->gram_by_update = false; }
     if (!c || !prox || !step_k) FAIL(PMX_E_INVALID, "NULL argument");
     HIP_CHECK(hipSetDevice(c->device));
-    int rc = check_prox(*prox, "prox_apply", true);
+    int rc = check_prox(*prox, "prox_apply", true, c->tab_set);
     if (rc != PMX_OK) return rc;
     float** slot; int64_t n;
     rc = buf_lookup(c, buf, &slot, &n, false);
     if (rc != PMX_OK) return rc;
-    rc = apply_prox_standalone(*slot, n / c->K, (int)c->K, *prox, step_k, c->colpart, c->stream);
+    rc = apply_prox_standalone(*slot, n / c->K, (int)c->K, *prox, step_k, c->colpart, c->stream, c->tabs);
     if (rc != PMX_OK) return rc;
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(c->stream));
     return PMX_OK;
 }
 
-extern "C" int pmx_prox_array(int device, float* X, int64_t rows, int K, const pmx_proxseq* prox, const float* step_k) {
+extern "C" int pmx_prox_table(pmx_ctx* c, int index, const pmx_prox* rows, int K) {
+    if (!c || !rows) FAIL(PMX_E_INVALID, "NULL argument");
+    if (index < 0 || index >= PMX_MAX_TABLES) FAIL(PMX_E_INVALID, "prox_table: index %d outside 0 .. %d", index, PMX_MAX_TABLES - 1);
+    if (K != c->K) FAIL(PMX_E_INVALID, "prox_table: %d rows for a context with K = %lld", K, (long long)c->K);
+    for (int k = 0; k < K; ++k)
+        if (!row_op_ok(rows[k].op)) FAIL(PMX_E_INVALID, "prox_table: row %d holds op %d, which is not an element-wise operator", k, rows[k].op);
+    HIP_CHECK(hipSetDevice(c->device));
+    int rc = dallocT(c, &c->tabs, (size_t)PMX_MAX_TABLES * MAXK);
+    if (rc != PMX_OK) return rc;
+    pmx_prox clean[MAXK] = {};
+    for (int k = 0; k < K; ++k) { clean[k].op = rows[k].op; clean[k].thresh = rows[k].thresh; clean[k].relative = rows[k].relative; }
+    // (stream-ordered behind the kernels already enqueued, which may read the slot's previous rows; `clean` is pageable: the copy has left it on return)
+    HIP_CHECK(hipMemcpyAsync(c->tabs + (size_t)index * MAXK, clean, sizeof(pmx_prox) * K, hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->tab_set[index] = true;
+    return PMX_OK;
+}
+
+static int prox_array_impl(int device, float* X, int64_t rows, int K, const pmx_proxseq* prox, const float* step_k, const pmx_prox* tables, int ntables) {
     if (!X || !prox || !step_k) FAIL(PMX_E_INVALID, "NULL argument");
     if (rows <= 0 || K <= 0 || K > MAXK) FAIL(PMX_E_INVALID, "bad shape rows=%lld K=%d", (long long)rows, K);
-    int rc = check_prox(*prox, "prox_array", true);
+    if (ntables < 0 || ntables > PMX_MAX_TABLES || (ntables > 0 && !tables)) FAIL(PMX_E_INVALID, "prox_array: bad table count %d", ntables);
+    int rc = check_prox(*prox, "prox_array", true, nullptr, ntables);
     if (rc != PMX_OK) return rc;
+    for (int64_t i = 0; i < (int64_t)ntables * K; ++i)
+        if (!row_op_ok(tables[i].op)) FAIL(PMX_E_INVALID, "prox_array: table row %lld holds op %d, which is not an element-wise operator", (long long)i, tables[i].op);
     HIP_CHECK(hipSetDevice(device));
     float* d = nullptr;
     const size_t bytes = (size_t)rows * K * sizeof(float), scratch = (size_t)2 * EW_BLOCKS * MAXK * sizeof(double);
-    HIP_CHECK(hipMalloc((void**)&d, bytes + scratch + 16));
+    const size_t tabBytes = (size_t)ntables * MAXK * sizeof(pmx_prox);         // device layout: MAXK rows per table
+    HIP_CHECK(hipMalloc((void**)&d, ((bytes + 15) / 16) * 16 + scratch + tabBytes + 16));
     double* colpart = reinterpret_cast<double*>(reinterpret_cast<char*>(d) + ((bytes + 15) / 16) * 16);
+    pmx_prox* dtab = ntables > 0 ? reinterpret_cast<pmx_prox*>(reinterpret_cast<char*>(colpart) + scratch) : nullptr;
     hipError_t e = hipMemcpy(d, X, bytes, hipMemcpyHostToDevice);
+    for (int t = 0; t < ntables && e == hipSuccess; ++t)
+        e = hipMemcpy(dtab + (size_t)t * MAXK, tables + (size_t)t * K, sizeof(pmx_prox) * K, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        rc = apply_prox_standalone(d, rows, K, *prox, step_k, colpart, nullptr);
+        rc = apply_prox_standalone(d, rows, K, *prox, step_k, colpart, nullptr, dtab);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpy(X, d, bytes, hipMemcpyDeviceToHost);
     }
     (void)hipFree(d);
     if (e != hipSuccess) FAIL(PMX_E_HIP, "prox_array: %s", hipGetErrorString(e));
     return PMX_OK;
+}
+extern "C" int pmx_prox_array(int device, float* X, int64_t rows, int K, const pmx_proxseq* prox, const float* step_k) {
+    return prox_array_impl(device, X, rows, K, prox, step_k, nullptr, 0);
+}
+extern "C" int pmx_prox_array_tables(int device, float* X, int64_t rows, int K, const pmx_proxseq* prox, const float* step_k,
+                                     const pmx_prox* tables, int ntables) {
+    return prox_array_impl(device, X, rows, K, prox, step_k, tables, ntables);
 }
 
 // [r6] scratch of pmx_bb_sums, one per device, kept between calls (the stepper calls this once per block and iteration: a hipMalloc / hipFree
@@ -2090,7 +2139,7 @@ extern "C" int pmx_pgm_begin(pmx_ctx* c, const pmx_pgm_params* p) {
     if (!p) FAIL(PMX_E_INVALID, "params is NULL");
     bool long_axis = false;
     for (int j = 0; j < 2; ++j) {
-        rc = check_prox(p->prox[j], j ? "prox_S" : "prox_A", true);
+        rc = check_prox(p->prox[j], j ? "prox_S" : "prox_A", true, c->tab_set);
         if (rc != PMX_OK) return rc;
         long_axis |= !p->host_prox[j] && prox_long_axis(p->prox[j]);
     }
@@ -2341,7 +2390,7 @@ static BtArgs bt_args(pmx_ctx* c) {
         u.X[j] = c->X[j]; u.Xe[j] = c->Xe[j]; u.Xp[j] = c->Xp[j]; u.G[j] = c->G[j];
         u.slab[j] = slab_ref(c, j);
         u.rows[j] = c->rows[j];
-        u.prox[j] = to_dev(p.prox[j]);
+        u.prox[j] = to_dev(p.prox[j], c->tabs);
         u.T[j] = (float)c->btT[j];
         u.Tb[j] = c->btBuf[j];
     }
@@ -2647,7 +2696,7 @@ extern "C" int pmx_adaprox_begin(pmx_ctx* c, const pmx_adaprox_params* p, int wa
     if (!(p->eps >= 0)) FAIL(PMX_E_INVALID, "eps < 0");                               // :333
     if (!(p->p > 0 && p->p <= 0.5)) FAIL(PMX_E_INVALID, "p out of (0,0.5]");           // :334
     for (int j = 0; j < 2; ++j) {
-        rc = check_prox(p->prox[j], j ? "prox_S" : "prox_A");
+        rc = check_prox(p->prox[j], j ? "prox_S" : "prox_A", false, c->tab_set);
         if (rc != PMX_OK) return rc;
     }
     if (c->f64) {                                // PMX_MODE_F64: this library's operators and step rule (or two constants), k64_ada_iter
@@ -2751,7 +2800,7 @@ static SubArgs sub_args(pmx_ctx* c, int t) {
         s.zb[j][0] = s_view(c, j, c->zb[j][0]);
         s.zb[j][1] = s_view(c, j, c->zb[j][1]);
         s.rows[j] = upd_rows(c, j);
-        s.prox[j] = to_dev(p.prox[j]);
+        s.prox[j] = to_dev(p.prox[j], c->tabs);
         s.e_rel[j] = p.e_rel[j];
         s.has_prox[j] = p.prox[j].n > 0;
     }
@@ -2837,7 +2886,7 @@ static int ada_enqueue_tail_fused(pmx_ctx* c, int it, double b1t, double b1prev)
     TailArgs t{};
     t.m = moment_args(c, it, b1t, b1prev, true);
     for (int j = 0; j < 2; ++j) {
-        t.prox[j] = to_dev(p.prox[j]);
+        t.prox[j] = to_dev(p.prox[j], c->tabs);
         t.e_rel[j] = p.e_rel[j];
         t.slots[j] = (int)((upd_rows(c, j) + 8191) / 8192);
     }
@@ -2911,7 +2960,7 @@ static Ada64Args ada64_args(pmx_ctx* c, int it, double b1t, double b1prev) {
         a.slab[j] = c->slabd[j];
         a.nslab[j] = j == 0 ? c->nSlabA : c->nSlabS;
         a.rows[j] = c->rows[j];
-        a.prox[j] = to_dev(p.prox[j]);
+        a.prox[j] = to_dev(p.prox[j], c->tabs);
         a.has_prox[j] = p.prox[j].n > 0;
         a.e_rel[j] = p.e_rel[j];
         a.fixed[j] = p.fixed_alpha[j];
@@ -3136,11 +3185,11 @@ extern "C" int pmx_bsdmm_begin(pmx_ctx* c, const pmx_bsdmm_params* p) {
     if (c->W || c->Wd_on)                              // bsdmm's steps come from nmf.step_pgm (nmf.py:187-193)
         FAIL(PMX_E_INVALID, "The truth value of an array with more than one element is ambiguous. Use a.any() or a.all()");
     for (int j = 0; j < 2; ++j) {
-        rc = check_prox(p->prox_f[j], j ? "prox_S" : "prox_A");
+        rc = check_prox(p->prox_f[j], j ? "prox_S" : "prox_A", false, c->tab_set);
         if (rc != PMX_OK) return rc;
         if (p->n_g[j] < 0 || p->n_g[j] > PMX_MAX_G) FAIL(PMX_E_UNSUPPORTED, "at most %d constraints per block", PMX_MAX_G);
         for (int i = 0; i < p->n_g[j]; ++i) {
-            rc = check_prox(p->prox_g[j][i], "proxs_g");
+            rc = check_prox(p->prox_g[j][i], "proxs_g", false, c->tab_set);
             if (rc != PMX_OK) return rc;
         }
     }
@@ -3188,12 +3237,12 @@ static BsdmmArgs bsdmm_args(pmx_ctx* c, int j) {
     BsdmmArgs u{};
     u.X = c->X[j];
     u.slab = slab_ref(c, j);
-    for (int i = 0; i < p.n_g[j]; ++i) { u.Z[i] = c->Zg[j][i]; u.U[i] = c->Ug[j][i]; u.prox_g[i] = to_dev(p.prox_g[j][i]); }
+    for (int i = 0; i < p.n_g[j]; ++i) { u.Z[i] = c->Zg[j][i]; u.U[i] = c->Ug[j][i]; u.prox_g[i] = to_dev(p.prox_g[j][i], c->tabs); }
     u.rows = c->rows[j];
     u.K = (int)c->K;
     u.j = j;
     u.n_g = p.n_g[j];
-    u.prox_f = to_dev(p.prox_f[j]);
+    u.prox_f = to_dev(p.prox_f[j], c->tabs);
     u.status = c->dstatus;
     u.partials = c->partials;
     return u;
@@ -3204,12 +3253,12 @@ static Bsdmm64Args bsdmm64_args(pmx_ctx* c, int j, int last_block) {
     u.X = c->Xd[j];
     u.slab = c->slabd[j];
     u.nslab = j == 0 ? c->nSlabA : c->nSlabS;
-    for (int i = 0; i < p.n_g[j]; ++i) { u.Z[i] = c->Zd[j][i]; u.U[i] = c->Ud[j][i]; u.prox_g[i] = to_dev(p.prox_g[j][i]); }
+    for (int i = 0; i < p.n_g[j]; ++i) { u.Z[i] = c->Zd[j][i]; u.U[i] = c->Ud[j][i]; u.prox_g[i] = to_dev(p.prox_g[j][i], c->tabs); }
     u.rows = c->rows[j];
     u.K = (int)c->K;
     u.j = j;
     u.n_g = p.n_g[j];
-    u.prox_f = to_dev(p.prox_f[j]);
+    u.prox_f = to_dev(p.prox_f[j], c->tabs);
     u.status = c->dstatus;
     u.e_rel = p.e_rel[j];
     u.e_abs = p.e_abs[j];

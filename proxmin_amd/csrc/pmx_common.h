@@ -81,6 +81,7 @@ enum { HALT_NONE = 0, HALT_CONVERGED = 1, HALT_NEED_SUB = 2, HALT_ERROR = 3,
 struct ProxSeq {           // device copy of pmx_proxseq
     int n, repeat;
     pmx_prox seq[PMX_MAX_SEQ];
+    const pmx_prox* tab;   // base of the per-component tables (PMX_PROX_COMPONENTS: table t at tab + t * MAXK), device memory; nullptr: none
 };
 
 __device__ __forceinline__ bool chain_halted(const DevStatus* st) {

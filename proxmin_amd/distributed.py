@@ -471,6 +471,26 @@ def _pair(v):
     return (v, v) if np.isscalar(v) else tuple(v)
 
 
+def _refuse_component_tables(prox_A, prox_S, proxs_g=None):
+    """Row-sharded runs do not carry per-component operator tables (PMX_PROX_COMPONENTS: an array `thresh` / `gamma`,
+    prox_components): NotImplementedError before a context or a process group is touched.  Callables that are no operators
+    of the library are left to the driver's own translation."""
+    from . import operators
+    members = [(prox_A, 0), (prox_S, 1)] + [(q, j) for j, g in enumerate(proxs_g or ()) for q in (g or ())]
+    for q, j in members:
+        if q is None:
+            continue
+        try:
+            seq = operators.device_proxseq(q, j)
+        except NotImplementedError:
+            if operators.is_components(q):
+                raise
+            continue
+        if operators.has_tables(seq):
+            raise NotImplementedError("row-sharded runs do not carry per-component operator parameters (an array thresh / gamma, "
+                                      "prox_components) of block %d: run them on one GPU" % j)
+
+
 @contextlib.contextmanager
 def _session(Y_local, A_local, S, prox_A, prox_S, group, device):
     """One rank's share of a sharded solve: -> (context with Y and the factors on the device, rank, world, the device
@@ -512,6 +532,7 @@ def nmf_adaprox_sharded(Y_local, A_local, S, M_global, prox_A=None, prox_S=None,
     Requires an initialised torch.distributed process group whose backend can reduce CUDA tensors
     (nccl = RCCL).  comm: "torch" (default) issues the collectives through torch.distributed, "native" through the C ABI's own
     RCCL entry points (pmx_comm_*; the process group only hands the communicator id around).  Returns (converged, iterations)."""
+    _refuse_component_tables(prox_A, prox_S)
     if not hasattr(b1, "__iter__"):
         b1 = np.array((b1,) * max_iter)
     b1 = np.asarray(b1, dtype=np.float64)
@@ -538,6 +559,7 @@ def nmf_pgm_sharded(Y_local, A_local, S, M_global, prox_A=None, prox_S=None, acc
     partial Gram matrix and the stopping sums riding in every chunk), each rank updates its N / world columns (and, under
     FISTA, extrapolates them), all-gather of the next evaluation point; any device prox_S (pgm applies it once, row by row of
     S^T).  Returns (converged, iterations)."""
+    _refuse_component_tables(prox_A, prox_S)
     with _session(Y_local, A_local, S, prox_A, prox_S, group, device) as (dev, rank, world, seqs):
         can_split = world > 1 and S.shape[1] % world == 0
         if s_split is True and not can_split:
@@ -556,6 +578,7 @@ def nmf_bsdmm_sharded(Y_local, A_local, S, M_global, prox_A=None, prox_S=None, p
     """Row-sharded `nmf(Y, A, S, algorithm=bsdmm, proxs_g=...)` for one rank.  Returns (converged, iterations)."""
     from . import operators
     proxs_g = proxs_g or [None, None]
+    _refuse_component_tables(prox_A, prox_S, proxs_g)
     seq_g = [None if g is None else [operators.device_proxseq(q, j) for q in g] for j, g in enumerate(proxs_g)]
     with _session(Y_local, A_local, S, prox_A, prox_S, group, device) as (dev, rank, world, seq_f):
         eng = ShardEngine(dev, world, rank, M_global, "bsdmm")

@@ -484,11 +484,46 @@ class DeviceNMF:
         _lib.check(self.lib.pmx_step_adaprox(self.h, _vp(out)))
         return out[: self.K].copy(), out[self.K:].copy()
 
+    # -- per-component operator tables (include/pmx.h: pmx_prox_table) --------------------------
+    def _stamp_tables(self, seqs, first=0):
+        """Upload the tables that device operator sequences carry (operators._seq: `seq.tables`) into this context's slots
+        first, first + 1, .. and return copies of the sequences whose PMX_PROX_COMPONENTS entries name those slots.  Every
+        table is checked before the first is written: ValueError for one without K rows, NotImplementedError for more tables
+        than the context has slots."""
+        from . import operators
+        operators.check_tables(seqs, self.K)
+        if first + sum(len(operators.seq_tables(q)) for q in seqs) > _lib.MAX_TABLES:
+            raise NotImplementedError("more than %d per-component operator tables in one call" % _lib.MAX_TABLES)
+        out, nxt = [], first
+        for q in seqs:
+            tables = operators.seq_tables(q)
+            if not tables:
+                out.append(q)
+                continue
+            c = _lib.ProxSeq.from_buffer_copy(q)
+            for i in range(c.n):
+                if c.seq[i].op == _lib.PROX["components"]:
+                    tab = tables[c.seq[i].reserved - 1]
+                    _lib.check(self.lib.pmx_prox_table(self.h, nxt, tab, len(tab)))
+                    c.seq[i].reserved = nxt + 1
+                    nxt += 1
+            out.append(c)
+        self._ntab = nxt
+        return out
+
+    def prox_apply(self, buf, seq, step_k):
+        """One operator sequence on a device buffer of the context in place (include/pmx.h: pmx_prox_apply); step_k: the K
+        per-component steps.  Tables go into the slots behind those of the running solver."""
+        seq, = self._stamp_tables([seq], first=getattr(self, "_ntab_solver", 0))
+        sk = np.ascontiguousarray(np.broadcast_to(np.asarray(step_k, dtype=np.float32).reshape(-1), (self.K,)))
+        _lib.check(self.lib.pmx_prox_apply(self.h, int(buf), C.byref(seq), _vp(sk)))
+
     # -- solvers ------------------------------------------------------------------------------
     def pgm_begin(self, prox, accelerated=False, step_scale=1.0, fixed_steps=None, e_rel=(1e-6, 1e-6), bb=None, backtracking=False,
                   host_prox=(False, False), unweighted_rule=False):
         p = _lib.PgmParams()
-        p.prox[0], p.prox[1] = prox
+        p.prox[0], p.prox[1] = self._stamp_tables(list(prox))
+        self._ntab_solver = self._ntab
         p.accelerated = int(bool(accelerated))
         p.step_scale = float(step_scale)
         p.use_fixed_steps = int(fixed_steps is not None)
@@ -542,7 +577,8 @@ class DeviceNMF:
                       prox_max_iter=1000, warm_moments=False, warm_vhat=False, fixed_alpha=None, e_rel=(1e-6, 1e-6),
                       host_step=False, host_prox=(False, False)):
         q = _lib.AdaproxParams()
-        q.prox[0], q.prox[1] = prox
+        q.prox[0], q.prox[1] = self._stamp_tables(list(prox))
+        self._ntab_solver = self._ntab
         q.scheme = _lib.SCHEME[scheme]
         q.b2, q.eps, q.p = float(b2), float(eps), float(p)
         q.check_convergence = int(bool(check_convergence))
@@ -585,14 +621,19 @@ class DeviceNMF:
             p.n_order = len(order)
             for i, j in enumerate(order):
                 p.order[i] = j
-        p.prox_f[0], p.prox_f[1] = prox_f
+        for j in range(2):
+            if len(proxs_g[j] or []) > _lib.MAX_G:
+                raise NotImplementedError("at most %d constraints per factor on the device" % _lib.MAX_G)
+        flat = self._stamp_tables(list(prox_f) + [ps for j in range(2) for ps in (proxs_g[j] or [])])
+        self._ntab_solver = self._ntab
+        p.prox_f[0], p.prox_f[1] = flat[:2]
+        at = 2
         for j in range(2):
             g = proxs_g[j] or []
-            if len(g) > _lib.MAX_G:
-                raise NotImplementedError("at most %d constraints per factor on the device" % _lib.MAX_G)
             p.n_g[j] = len(g)
-            for i, ps in enumerate(g):
-                p.prox_g[j][i] = ps
+            for i in range(len(g)):
+                p.prox_g[j][i] = flat[at]
+                at += 1
             p.e_rel[j], p.e_abs[j] = float(e_rel[j]), float(e_abs[j])
         _lib.check(self.lib.pmx_bsdmm_begin(self.h, C.byref(p)))
 

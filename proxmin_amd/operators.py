@@ -9,6 +9,10 @@ Two uses:
     never called on that path;
   * called directly on an ndarray they run the same device kernel on that array
     (`pmx_prox_array`): there is no NumPy implementation in this package.
+
+Per-component parameters: `thresh` (`gamma`) of the threshold operators may be an array with one value per component, and
+`prox_components` gives every component an operator of its own.  Both become one device entry PMX_PROX_COMPONENTS whose
+table holds one (op, thresh, relative) row per component (include/pmx.h: pmx_prox_table).
 """
 from __future__ import annotations
 
@@ -20,28 +24,117 @@ import numpy as np
 from . import _lib
 
 __all__ = ["prox_id", "prox_zero", "prox_plus", "prox_unity", "prox_unity_plus", "prox_min", "prox_max",
-           "prox_hard", "prox_hard_plus", "prox_soft", "prox_soft_plus", "prox_max_entropy", "AlternatingProjections"]
+           "prox_hard", "prox_hard_plus", "prox_soft", "prox_soft_plus", "prox_max_entropy", "prox_components",
+           "AlternatingProjections"]
 
 
 # ---------------------------------------------------------------------------------------------
 # direct application on host arrays
 # ---------------------------------------------------------------------------------------------
+# operators that work entry by entry: what a row of a per-component table may be (include/pmx.h: pmx_prox_table)
+ELEMENTWISE = ("id", "zero", "plus", "min", "max", "hard", "hard_plus", "soft", "soft_plus", "max_entropy")
+
+
 def _seq(entries, repeat=1):
+    """entries: (op, unit, thresh, relative), or ("components", 0, rows, 0) with rows = [(op, thresh, relative)] * K: the rows
+    go into `ps.tables` (a Python attribute: a list of K-row _lib.Prox arrays) and the entry's `reserved` is 1 + its index there.
+    The engine uploads the tables and re-stamps `reserved` with the context's own index (engine.DeviceNMF._stamp_tables)."""
     ps = _lib.ProxSeq()
     ps.n = len(entries)
     ps.repeat = repeat
+    ps.tables = []
     for i, (op, unit, thresh, relative) in enumerate(entries):
+        if op == "components":
+            tab = (_lib.Prox * len(thresh))()
+            for k, (rop, rth, rrel) in enumerate(thresh):
+                assert rop in ELEMENTWISE
+                tab[k].op, tab[k].thresh, tab[k].relative = _lib.PROX[rop], float(rth), int(rrel)
+            ps.tables.append(tab)
+            ps.seq[i].op, ps.seq[i].reserved = _lib.PROX["components"], len(ps.tables)
+            continue
         ps.seq[i].op, ps.seq[i].unit, ps.seq[i].thresh, ps.seq[i].relative = _lib.PROX[op], unit, float(thresh), int(relative)
     return ps
+
+
+def seq_tables(seq):
+    """the per-component tables a device operator sequence carries (a list of K-row _lib.Prox arrays; [] for none)"""
+    return list(getattr(seq, "tables", None) or [])
+
+
+def table_rows(tab):
+    """one table as [(op code, thresh, relative)] * K"""
+    return [(int(r.op), float(r.thresh), int(r.relative)) for r in tab]
+
+
+def check_tables(seqs, K):
+    """Every per-component table of these sequences has one row per component of the problem: ValueError otherwise (where the
+    reference's broadcast of the thresholds against the factor would fail)."""
+    for seq in seqs:
+        for tab in seq_tables(seq):
+            if len(tab) != K:
+                raise ValueError("per-component operator parameters: %d values for a factorisation with K = %d components" % (len(tab), K))
 
 
 def _run_rows(rows2d, ps, step_k):
     lib = _lib.require_gpu()
     buf = np.ascontiguousarray(rows2d, dtype=np.float32)
     sk = np.ascontiguousarray(np.broadcast_to(np.asarray(step_k, dtype=np.float32).reshape(-1), (buf.shape[1],)))
+    tables = seq_tables(ps)
+    if tables:                           # per-component rows: pmx_prox_array_tables takes them next to the sequence
+        check_tables([ps], buf.shape[1])
+        flat = (_lib.Prox * (len(tables) * buf.shape[1]))()
+        for t, tab in enumerate(tables):
+            C.memmove(C.byref(flat, t * buf.shape[1] * C.sizeof(_lib.Prox)), tab, C.sizeof(tab))
+        _lib.check(lib.pmx_prox_array_tables(0, buf.ctypes.data_as(C.c_void_p), buf.shape[0], buf.shape[1], C.byref(ps),
+                                             sk.ctypes.data_as(C.c_void_p), flat, len(tables)))
+        return buf
     _lib.check(lib.pmx_prox_array(0, buf.ctypes.data_as(C.c_void_p), buf.shape[0], buf.shape[1], C.byref(ps),
                                   sk.ctypes.data_as(C.c_void_p)))
     return buf
+
+
+def _scalar_or_array(thresh):
+    """-> (float, None) for a scalar or a size-1 array, (None, float64 array) for anything larger"""
+    if np.ndim(thresh) == 0:
+        return float(thresh), None
+    arr = np.asarray(thresh, dtype=np.float64)
+    if arr.size == 1:
+        return float(arr.reshape(-1)[0]), None
+    return None, arr
+
+
+def _component_axis(shape, X_shape):
+    """Which axis of a 2-D X an array of this shape indexes when it broadcasts one value per component: 1 for (K,) / (1, K) with
+    K = X.shape[1] (how A holds its components), 0 for (K, 1) with K = X.shape[0] (S); None: it does not."""
+    if len(X_shape) != 2:
+        return None
+    if shape in ((X_shape[1],), (1, X_shape[1])):
+        return 1
+    if shape == (X_shape[0], 1):
+        return 0
+    return None
+
+
+def _apply_rows(X, step, rows, axis):
+    """One per-component table (rows[k] = (op, thresh, relative) of component k along `axis` of the 2-D X) on X in place."""
+    K = X.shape[axis]
+    if K > _lib.MAXK:
+        raise NotImplementedError("per-component operator parameters for %d components (at most %d)" % (K, _lib.MAXK))
+    if len(rows) != K:
+        raise ValueError("per-component operator parameters: %d values for %d components along axis %d of X %s" % (len(rows), K, axis, X.shape))
+    step_arr = np.asarray(step, dtype=np.float64)
+    if step_arr.ndim == 0 or step_arr.size == 1:
+        sk = float(step_arr.reshape(-1)[0]) if step_arr.size else 0.0
+    elif _component_axis(step_arr.shape, X.shape) == axis:
+        sk = step_arr.reshape(-1)
+    else:
+        raise NotImplementedError("step of shape %s next to per-component parameters along axis %d of X %s" % (step_arr.shape, axis, X.shape))
+    ps = _seq([("components", 0, rows, 0)])
+    if axis == 1:
+        X[...] = _run_rows(X, ps, sk)
+    else:
+        X[...] = _run_rows(X.T, ps, sk).T
+    return X
 
 
 def _apply(X, step, op, axis=None, thresh=0.0, kind="relative"):
@@ -64,6 +157,13 @@ def _apply(X, step, op, axis=None, thresh=0.0, kind="relative"):
         for c0 in range(0, Wm.shape[1], _lib.MAXK):
             Wm[:, c0:c0 + _lib.MAXK] = _run_rows(np.ascontiguousarray(Wm[:, c0:c0 + _lib.MAXK]), _seq([(op, 1, 0.0, 0)]), 0.0)
         return X
+    thresh, per_k = _scalar_or_array(thresh)
+    if per_k is not None:               # one threshold per component: the shapes that broadcast along X's components
+        axis = _component_axis(per_k.shape, X.shape)
+        if axis is None:
+            raise NotImplementedError("thresh of shape %s on X of shape %s: per-component thresholds only ((K,) / (1, K) along axis 1, "
+                                      "(K, 1) along axis 0); per-row and per-element thresholds are not built" % (per_k.shape, X.shape))
+        return _apply_rows(X, step, [(op, t, rel) for t in per_k.reshape(-1)], axis)
     ps = _seq([(op, 0, thresh, rel)])
     if step_arr.ndim == 0 or step_arr.size == 1 or not rel or op in ("id", "zero", "plus"):
         flat = X.reshape(-1)
@@ -110,32 +210,45 @@ def prox_unity_plus(X, step, axis=0):
 
 
 def prox_min(X, step, thresh=0, type="relative"):
-    """Projection onto numbers above `thresh` (operators.py:55-68)."""
+    """Projection onto numbers above `thresh` (operators.py:55-68).
+    `thresh` may be an array with one value per component ((K,) / (1, K) next to an M x K array, (K, 1) next to a K x N one):
+    component k is projected onto numbers above thresh[k] -- the evident broadcast; the reference raises on an array here
+    (boolean-index assignment of an array).  Arrays per row or per element raise NotImplementedError."""
     return _apply(X, step, "min", thresh=thresh, kind=type)
 
 
 def prox_max(X, step, thresh=0, type="relative"):
-    """Projection onto numbers below `thresh` (operators.py:71-84)."""
+    """Projection onto numbers below `thresh` (operators.py:71-84).
+    `thresh` may be an array with one value per component, as for prox_min: component k is projected onto numbers below
+    thresh[k] (the reference raises on an array here).  Arrays per row or per element raise NotImplementedError."""
     return _apply(X, step, "max", thresh=thresh, kind=type)
 
 
 def prox_hard(X, step, thresh=0, type="relative"):
-    """Hard thresholding (operators.py:109-124)."""
+    """Hard thresholding (operators.py:109-124).
+    `thresh` may be an array with one value per component ((K,) / (1, K) next to an M x K array, (K, 1) next to a K x N one),
+    as in the reference, where it broadcasts; arrays per row or per element raise NotImplementedError (not built)."""
     return _apply(X, step, "hard", thresh=thresh, kind=type)
 
 
 def prox_hard_plus(X, step, thresh=0, type="relative"):
-    """Hard thresholding with projection onto non-negative numbers (operators.py:127-135)."""
+    """Hard thresholding with projection onto non-negative numbers (operators.py:127-135).
+    `thresh` may be an array with one value per component ((K,) / (1, K) next to an M x K array, (K, 1) next to a K x N one),
+    as in the reference, where it broadcasts; arrays per row or per element raise NotImplementedError (not built)."""
     return _apply(X, step, "hard_plus", thresh=thresh, kind=type)
 
 
 def prox_soft(X, step, thresh=0, type="relative"):
-    """Soft thresholding (operators.py:138-150)."""
+    """Soft thresholding (operators.py:138-150).
+    `thresh` may be an array with one value per component ((K,) / (1, K) next to an M x K array, (K, 1) next to a K x N one),
+    as in the reference, where it broadcasts; arrays per row or per element raise NotImplementedError (not built)."""
     return _apply(X, step, "soft", thresh=thresh, kind=type)
 
 
 def prox_soft_plus(X, step, thresh=0, type="relative"):
-    """Soft thresholding with projection onto non-negative numbers (operators.py:153-160)."""
+    """Soft thresholding with projection onto non-negative numbers (operators.py:153-160).
+    `thresh` may be an array with one value per component ((K,) / (1, K) next to an M x K array, (K, 1) next to a K x N one),
+    as in the reference, where it broadcasts; arrays per row or per element raise NotImplementedError (not built)."""
     return _apply(X, step, "soft_plus", thresh=thresh, kind=type)
 
 
@@ -145,7 +258,11 @@ def prox_max_entropy(X, step, gamma=1, type="relative"):
     y + gamma_ ln y = x - gamma_, i.e. gamma_ W(exp(x / gamma_ - 1) / gamma_) with the principal Lambert W.
     Entries <= 0, NaN and -inf keep their value, +inf stays +inf (so the operator jumps at 0, as the reference's does).
 
-    Three differences from the reference, all of them where the reference has no usable answer:
+    `gamma` may be an array with one value per component ((K,) / (1, K) next to an M x K array, (K, 1) next to a K x N one):
+    component k is regularised with gamma[k] -- the evident broadcast, on which the reference raises (a broadcast error); arrays
+    per row or per element raise NotImplementedError.
+
+    Three more differences from the reference, all of them where the reference has no usable answer:
       * the equation is solved in the log domain, so the result is finite for every finite x > 0 -- the reference's
         exp(x / gamma_ - 1) overflows to inf above 88.7 (float32 arrays) / 709 (float64);
       * a per-component or per-element `step` with type="relative" (what adaprox passes; step arrays in pgm) applies
@@ -161,6 +278,50 @@ def prox_max_entropy(X, step, gamma=1, type="relative"):
         X[keep] = kept
         return X
     return _apply(X, step, "max_entropy", thresh=gamma, kind=type)
+
+
+def _component_rows(prox, K, block=None):
+    """The table of prox_components(prox=...) over K components, [(op, thresh, relative)] * K -- or None when a member is not
+    an element-wise operator of this module with scalar parameters (bare or a keyword-only partial)."""
+    members = list(prox) if isinstance(prox, (list, tuple)) else [prox] * K
+    rows = []
+    for q in members:
+        try:
+            e = _one_entry(q, 0 if block is None else block)
+        except NotImplementedError:
+            return None
+        if e is None or e[0] not in ELEMENTWISE:
+            return None
+        rows.append((e[0], e[2], e[3]))
+    return rows
+
+
+def prox_components(X, step, prox=None, axis=0):
+    """Component k of X along `axis` (X[k] for axis=0, X[:, k] for axis=1) gets its own operator prox[k](., step), in place
+    (the contract of operators.py:87-103, whose body reads an undefined name and cannot run).  `prox` is one callable -- every
+    component gets it -- or a list with one callable per component (ValueError for another length).
+
+    Members that are element-wise operators of this module with scalar parameters run as ONE device kernel with a
+    per-component table (2-D X, at most 128 components); any other callable is called on its component's host view.
+    Difference from the reference's contract: a per-component `step` -- shape (K,) / (1, K) with axis=1, (K, 1) with axis=0,
+    what adaprox passes -- reaches member k as component k's own step; the reference would hand every member the whole array."""
+    X = np.asarray(X) if not isinstance(X, np.ndarray) else X
+    if axis not in (0, 1) or X.ndim <= axis:
+        raise NotImplementedError("prox_components: axis %r of an array of shape %s" % (axis, X.shape))
+    K = X.shape[axis]
+    members = list(prox) if isinstance(prox, (list, tuple)) else [prox] * K
+    if len(members) != K:
+        raise ValueError("prox_components: %d operators for %d components along axis %d of X %s" % (len(members), K, axis, X.shape))
+    if X.ndim == 2 and K <= _lib.MAXK:
+        rows = _component_rows(members, K)
+        if rows is not None:
+            return _apply_rows(X, step, rows, axis)
+    step_arr = np.asarray(step)
+    per_k = step_arr.size > 1 and _component_axis(step_arr.shape, X.shape) == axis
+    for k in range(K):
+        Xk = X[k] if axis == 0 else X[:, k]
+        Xk[...] = members[k](Xk, step_arr.reshape(-1)[k] if per_k else step)
+    return X
 
 
 class AlternatingProjections(object):
@@ -195,7 +356,7 @@ class AlternatingProjections(object):
 # ---------------------------------------------------------------------------------------------
 _BY_FUNC = {prox_id: "id", prox_zero: "zero", prox_plus: "plus", prox_unity: "unity", prox_unity_plus: "unity_plus",
             prox_min: "min", prox_max: "max", prox_hard: "hard", prox_hard_plus: "hard_plus",
-            prox_soft: "soft", prox_soft_plus: "soft_plus", prox_max_entropy: "max_entropy"}
+            prox_soft: "soft", prox_soft_plus: "soft_plus", prox_max_entropy: "max_entropy", prox_components: "components"}
 
 
 def _one_entry(prox, block):
@@ -216,12 +377,40 @@ def _one_entry(prox, block):
         return (op, unit, 0.0, 0)
     if op in ("id", "zero", "plus"):
         return None if kw else (op, 0, 0.0, 0)
+    if op == "components":
+        # fused when `axis` is the block's component axis (1 for A, 0 for S: unit == 0 above) and every member is an element-wise
+        # operator with scalar parameters; everything else is a user prox (plain NotImplementedError: the host route)
+        members, axis = kw.pop("prox", None), kw.pop("axis", 0)
+        if kw or members is None:
+            return None
+        if axis != (1 if block == 0 else 0):
+            raise NotImplementedError("prox_components along axis %r of block %d: fused along the component axis only (axis=1 on A, "
+                                      "axis=0 on S)" % (axis, block))
+        if not isinstance(members, (list, tuple)):             # one callable for every component: the operator itself
+            rows = _component_rows(members, 1, block)
+            if rows is None:
+                raise NotImplementedError("prox_components of %r: not an element-wise operator of proxmin_amd.operators" % (members,))
+            return (rows[0][0], 0, rows[0][1], rows[0][2])
+        rows = _component_rows(members, len(members), block)
+        if rows is None or not rows:
+            raise NotImplementedError("prox_components with a member that is not an element-wise operator of proxmin_amd.operators "
+                                      "with scalar parameters: %r" % (members,))
+        return ("components", 0, rows, 0)
     thresh = kw.pop("gamma", 1) if op == "max_entropy" else kw.pop("thresh", 0)
     kind = kw.pop("type", "relative")
     if kw:
         return None
     assert kind in ["relative", "absolute"]
-    return (op, 0, float(thresh), kind == "relative")
+    thresh, per_k = _scalar_or_array(thresh)
+    if per_k is not None:
+        # one value per component: (K,) / (1, K) on A (M x K), (K, 1) on S (K x N); the reference would also broadcast per-row
+        # and per-element shapes, which are not built
+        ok = per_k.ndim == 2 and per_k.shape[1] == 1 if block == 1 else (per_k.ndim == 1 or (per_k.ndim == 2 and per_k.shape[0] == 1))
+        if not ok:
+            raise NotImplementedError("%s of shape %s on block %d: per-component values only ((K,) or (1, K) on A, (K, 1) on S); "
+                                      "per-row and per-element shapes are not built" % ("gamma" if op == "max_entropy" else "thresh", per_k.shape, block))
+        return ("components", 0, [(op, t, kind == "relative") for t in per_k.reshape(-1)], 0)
+    return (op, 0, thresh, kind == "relative")
 
 
 class NotFusable(NotImplementedError):
@@ -230,6 +419,16 @@ class NotFusable(NotImplementedError):
     application: for_solver="pgm") unless the call has a line search, a user grad / step / prox or fp64 kernels; adaprox,
     bsdmm and those pgm calls apply it between kernel launches by calling it on the host copy of its argument -- which
     runs the stand-alone device operator kernel -- one iteration per call."""
+
+
+def has_tables(seq):
+    """Does a device operator sequence hold a per-component entry (PMX_PROX_COMPONENTS)?"""
+    return any(seq.seq[i].op == _lib.PROX["components"] for i in range(seq.n))
+
+
+def is_components(prox):
+    """prox_components, bare or as a partial (whatever its members)"""
+    return (prox.func if isinstance(prox, functools.partial) else prox) is prox_components
 
 
 def has_long_axis(seq):
