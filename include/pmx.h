@@ -25,8 +25,8 @@
 extern "C" {
 #endif
 
-#define PMX_ABI_VERSION 7 /* v7 grew, additively, by one op code (PMX_PROX_COMPONENTS) and two symbols (pmx_prox_table,
-                             pmx_prox_array_tables): no struct changed its layout, so the number stayed */
+#define PMX_ABI_VERSION 7 /* v7 grew, additively, by one op code (PMX_PROX_COMPONENTS) and three symbols (pmx_prox_table,
+                             pmx_prox_array_tables, pmx_gfix_info): no struct changed its layout, so the number stayed */
 
 /* ---- status codes -------------------------------------------------------------------- */
 enum {
@@ -273,6 +273,12 @@ int pmx_time_grad(pmx_ctx* ctx, int do_A, int do_S, int reps, double* avg_ms);
  * + 1000 x times it left the fused adaprox tail (k_ada_tail) + 1000000 if that tail is in use now + 10000000 if a two-term fp16 kernel
  * refused the residual's range and the context went on in exact fp32 (PMX_MODE_F16X2 above; info[0] then names the fp32 kernel). */
 int pmx_k1_info(pmx_ctx* ctx, int info[8]);
+/* [ABI v7] Who formed the K x K correction of PMX_MODE_F16X2R's gradient passes in this context so far: info[0] = K1 launches that
+ * carried its three stages themselves (k_grad_f16_v8<.., GF>: K1's K = 64, both gradients wanted), info[1] = times the three
+ * stand-alone launches (k_gfix_gram / _reduce / _apply) were enqueued behind K1, info[2] = 1 once a carried correction missed an
+ * arrival and the context fell back to the stand-alone launches for good, info[3] = such faults.  The slab is the same bit for bit
+ * either way.  (PMX_K1_GFIX=0 in the environment, read at every launch: the stand-alone launches.) */
+int pmx_gfix_info(pmx_ctx* ctx, int info[4]);
 
 /* ---- single operations (unit parity tests, and what the reference exposes as functions) --- */
 /* nmf.grad_likelihood, W=1 (nmf.py:28-41): gradients at the current A, St into GA / GST.     */

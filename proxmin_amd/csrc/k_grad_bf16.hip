@@ -26,6 +26,7 @@
 // (same slab scheme as k_grad.hip; gSt gets two slabs per row region, one per row half).
 #include <stdlib.h>
 #include "pmx_common.h"
+#include "k_gfix_dev.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -872,6 +873,7 @@ struct GradV4Args {
     int consPrio;        // [r6] s_setprio level of the CONSUMER waves for the launch (0: none): the consumers are the pole of every slot, the producers wait ~30 % of it at the barrier
     K1GramFold fold;     // [r6] k_grad_f16_k32: the step rule's Gram fold riding in the first workgroups (pmx_common.h)
     int y16;             // [r7] k_grad_f16_v8<.., HH>: Y can be fetched sixteen bytes per lane (ldY % 4 == 0, 16-byte-aligned base): the <.., Y16> instances
+    GfixRide gfix;       // k_grad_f16_v8<.., HH, RS, .., GF>: the K x K correction's three stages on this launch's idle waves (k_gfix_dev.h); seq = 0: none
 };
 
 // (k_grad_bf16_v4's kernel was removed in round 4 together with k_grad_bf16_v5's: with K1's zero-padded frame -- pmx_k1_frame -- the

@@ -168,8 +168,23 @@ static_assert(V8_LDS_BYTES <= 160 * 1024, "");
 // per value, in the epilogue step that reads the value): eight global_load_dwordx4 per block pair instead of sixteen dwordx2, each 4 rows x 256
 // contiguous bytes, eight offset registers instead of sixteen, still 64 registers of Y in flight.  Every Y value reaches the subtraction it reached before:
 // gradients bit for bit those of the 8-byte fetch.
-template <bool PROF, bool HASW, bool CHAIN, bool LOSS, bool R3 = false, bool HH = false, bool RS = false, bool ONLYS = false, bool Y16 = false>
+// GF: the K x K correction of <HH> (k_gfix.hip) formed by THIS launch instead of three launches behind it (<HH, RS> only; GradV4Args::gfix armed by the host).
+// The correction depends on the factors alone, not on anything K1 computes, and K1's waves idle at both ends of the launch with their registers free:
+//   gram     the four consumer waves, between the "Sl published" barrier and their first sync(): the workgroup's shares of k_gfix_gram's 256 workgroups (dealt
+//            round-robin), wave j in that kernel's role W = j, with scA / scS (the same maxima, the same formula as gfix_scale); partials stored write-through,
+//            one arrival word per workgroup behind the first sync()
+//   reduce   the four producer waves behind their last barrier (they finish two slots before the consumers): the workgroup's shares of k_gfix_reduce's 256
+//            blocks, behind a bounded wait for every gram arrival of the launch (stored ~a launch earlier: it passes at the first look); Q stored write-through
+//   apply    all eight waves behind the loss reduction: a bounded wait for every reduce arrival (the ONE wait of the ride that is exposed), the other factor's Q
+//            staged into the launch's dead LDS (k_gfix_apply's planes), k_gfix_apply's tasks into the correction slab -- the first half of the grid corrects gA,
+//            the rest gSt.  Plain stores: the slab is read by the next launch.
+// The stages are k_gfix_dev.h's, the code the stand-alone kernels run: the slab is the same bit for bit.  A wait that expires (workgroups not co-resident) reports
+// k1_fault = K1_FAULT_GFIX and halts the chain of kernels; the host repeats the iteration with the stand-alone launches and keeps them (chain_fault_fallback).
+// What the stages need of the thread index is derived where they run (gfix_ride_tid), so that nothing is carried through the loops: the instances spill what
+// their counterparts without the ride spill (tests/test_build_resources_gfix.py).
+template <bool PROF, bool HASW, bool CHAIN, bool LOSS, bool R3 = false, bool HH = false, bool RS = false, bool ONLYS = false, bool Y16 = false, bool GF = false>
 __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
+    static_assert(!GF || (HH && RS), "GF: the K x K correction rides in the <HH, RS> gradient pass");
     static_assert(!Y16 || (HH && !PROF && !LOSS), "Y16: the <HH> gradient passes (W shares Y's sixteen offsets: weighted instances keep the 8-byte fetch)");
     static_assert(!ONLYS || (HH && !RS && !CHAIN && !PROF && !LOSS), "ONLYS: an instance of the <HH> gradient pass without gA");
     static_assert(!(R3 && HH) && !(HH && HASW), "HH: unweighted contexts, instead of the third terms");
@@ -217,6 +232,7 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
     const bool producer = w < 4;          // (the "no Y traffic" ablation switch of the older variants is not implemented here)
     const int j = w & 3;                     // index within the role
     float lossAcc = 0.f;
+    bool gfOk = true;                        // GF, producers: this wave has run its part of the reduce shares
     unsigned long long ph[PROF ? 10 : 1] = {};
     const bool prof = PROF && a.prof != nullptr && (w == 0 || w == 4);
 #define PH(i) if constexpr (PROF) { if (prof) { const unsigned long long t_ = __builtin_readcyclecounter(); ph[i] += t_ - tprev; tprev = t_; } }
@@ -596,6 +612,21 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
         slot(nrp, c1{}, p1, p0, q1, q0, no{}, no{});
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();              // (pairs with the consumers' barrier between parking and merging their gSt row halves)
+        if constexpr (GF) {
+            // GF: the producers are done two slots before the consumers -- the workgroup's shares of the REDUCE stage, one k_gfix_reduce block each.  Every gram
+            // share of the launch was stored ~a launch ago (the wait normally passes at its first look).
+            if (blockIdx.x < GFIX_RIDE_WGS) {
+                const int nwg = (int)gridDim.x < GFIX_RIDE_WGS ? (int)gridDim.x : GFIX_RIDE_WGS;
+                // share sh = k_gfix_reduce's block (sh % GFIX_PARTS, sh / GFIX_PARTS) of its grid (4 n / 256, 2), n = 2 K^2: as many blocks per factor as gram parts
+                static_assert(K == 64 && 4 * 2 * K * K / 256 == GFIX_PARTS && GFIX_RIDE_WGS == 2 * GFIX_PARTS, "the reduce shares are dealt like the gram shares");
+                const int t2 = gfix_ride_tid();
+                gfOk = gfix_ride_wait(a.gfix.arrive, nwg, a.gfix.seq, a.status, a.wstatus, t2 & 63);
+                if (gfOk) {
+                    for (int sh = blockIdx.x; sh < GFIX_RIDE_WGS; sh += (int)gridDim.x) gfix_reduce_share<true>(a.gfix.part, a.gfix.Q, K, sh / GFIX_PARTS, sh % GFIX_PARTS, t2);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // Q is in memory before the workgroup's arrival (behind the next barrier)
+                }
+            }
+        }
     } else if constexpr (RS) {
         // ================================ consumers, roles split by contraction (see RS in the header) ==============
         k1_set_priority(a.consPrio);
@@ -609,6 +640,26 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
             const int kk = k0 + 16 * (lq & 1) + 4 * (li & 3);
             return row * ROWB + ((((kk >> 3) ^ v3_swz(row)) & 7) << 4) + 8 * ((kk >> 2) & 1);
         };
+        if constexpr (GF) {
+            // GF: the consumers have nothing to do until slot 2 -- the workgroup's shares of the GRAM stage (k_gfix_gram's workgroups, dealt round-robin), wave j in
+            // k_gfix_gram's role W = j, with the scales this kernel has just derived from the same maxima by the same formula.  The arrival goes out behind the
+            // first sync() below (all four waves have drained their stores by then).  The rows are requested HERE, behind the barrier: the first batch of the
+            // workgroup's first share requested at the top of the kernel, next to sr[], measured the same on one box (four alternating runs per flag set: 2618 -
+            // 2681 against 2569 - 2664 it/s at 20 / 5, 2754 - 2782 against 2772 - 2808 at 100 / 20; profiles/gfix_in_k1_ab.txt) and cost the instances with
+            // one gA slab per column region three more spilled registers (4, 20 bytes of scratch: over their pin).
+            const int t2 = gfix_ride_tid(), lane2 = t2 & 63;
+            const int jw = __builtin_amdgcn_readfirstlane((t2 >> 6) & 3);
+            for (int sh = blockIdx.x; sh < GFIX_RIDE_WGS; sh += (int)gridDim.x) {
+                const int f = sh / GFIX_PARTS, part = sh % GFIX_PARTS;
+                const float* Xf = f ? a.St : a.A;
+                const float sc = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, f ? scS : scA)));
+                if (jw == 0) gfix_gram_one<2, 0, true, 2>(Xf, a.gfix.rows[f], part, a.gfix.part, f, sc, lane2);
+                else if (jw == 1) gfix_gram_one<2, 1, true, 2>(Xf, a.gfix.rows[f], part, a.gfix.part, f, sc, lane2);
+                else if (jw == 2) gfix_gram_one<2, 2, true, 2>(Xf, a.gfix.rows[f], part, a.gfix.part, f, sc, lane2);
+                else gfix_gram_one<2, 3, true, 2>(Xf, a.gfix.rows[f], part, a.gfix.part, f, sc, lane2);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
         if (j < 2) {
             // ---- gA: rows 64 j .. 64 j + 63 of the panel (row tiles rt = 0, 1), both k tiles --------------------------------
             f32x16 accA[2][2];
@@ -652,6 +703,9 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
                 if (a.chainInject && blockIdx.x == 0 && j == 0) link.fault(3);
             }
             sync();
+            if constexpr (GF) {
+                if (j == 0 && lane == 0 && blockIdx.x < GFIX_RIDE_WGS) __hip_atomic_store(a.gfix.arrive + blockIdx.x, a.gfix.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
             sync();
             int s = 2;
             // [r6] The previous sum of the panel arrives in four pieces (accumulator registers 4 p .. 4 p + 3 of all four tiles), piece p added behind the MFMAs of
@@ -1015,11 +1069,64 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
         __syncthreads();
         float* red = reinterpret_cast<float*>(smem);
         if (lane == 0) red[w] = v;
+        if constexpr (GF) {
+            if (lane == 0 && producer) red[16 + w] = gfOk ? 1.f : 0.f;
+        }
         __syncthreads();
         if (tid == 0) {
             double s = 0.0;
             for (int i = 0; i < 4; ++i) s += (double)red[i];
             a.lossPart[blockIdx.x] = s;
+        }
+    }
+    if constexpr (GF) {
+        // GF: the APPLY stage on all eight waves, in the launch's dead LDS (k_gfix_apply's planes: 36 KB behind the words used above).  The only wait of the ride
+        // that is exposed: every reduce share of the launch -- they run at the ends of the first GFIX_RIDE_WGS workgroups.
+        float* red = reinterpret_cast<float*>(smem);
+        const int nwg = (int)gridDim.x < GFIX_RIDE_WGS ? (int)gridDim.x : GFIX_RIDE_WGS;
+        const int tid = gfix_ride_tid(), lane = tid & 63, w = tid >> 6, l31 = lane & 31, hi = lane >> 5;      // (shadow the kernel's: see gfix_ride_tid)
+        if (w == 0) {
+            if (a.gfix.inject && blockIdx.x == 0 && lane == 0) {       // tests: the report alone (the host repeats the iteration with the stand-alone launches)
+                a.wstatus->k1_fault = K1_FAULT_GFIX;
+                a.wstatus->reason = HALT_ERROR;
+                __threadfence();
+                a.wstatus->halt = 1;
+            }
+            const bool mine = red[16] != 0.f && red[17] != 0.f && red[18] != 0.f && red[19] != 0.f;
+            if (mine && lane == 0 && blockIdx.x < GFIX_RIDE_WGS)
+                __hip_atomic_store(a.gfix.arrive + GFIX_RIDE_WGS + blockIdx.x, a.gfix.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const bool go = gfix_ride_wait(a.gfix.arrive + GFIX_RIDE_WGS, nwg, a.gfix.seq, a.status, a.wstatus, lane);
+            if (lane == 0) red[24] = go ? 1.f : 0.f;
+        }
+        __syncthreads();
+        if (red[24] == 0.f) return;
+        // a workgroup stages ONE factor's matrices: the first half of the grid corrects gA, the rest gSt (a grid of one workgroup: both, one after the other)
+        const int G = (int)gridDim.x, half = G / 2;
+        const int fBeg = G >= 2 ? ((int)blockIdx.x < half ? 0 : 1) : 0, fEnd = G >= 2 ? fBeg + 1 : 2;
+        const int gidx = G >= 2 && fBeg == 1 ? (int)blockIdx.x - half : (int)blockIdx.x, gsize = G >= 2 ? (fBeg == 1 ? G - half : half) : 1;
+        float* redq = reinterpret_cast<float*>(smem + 128);
+        _Float16* qpl = reinterpret_cast<_Float16*>(smem + 256);
+        static_assert(256 + 4 * K * (K + 8) * 2 <= V8_LDS_BYTES, "");
+        for (int f = fBeg; f < fEnd; ++f) {
+            const float* X = f ? a.St : a.A;
+            const int64_t rows = a.gfix.rows[f];
+            const float sc = gfix_scale_wave(a.absmax, f, lane);       // scA / scS again (not carried through the launch in a register)
+            const int64_t ntask = (rows + 31) / 32 * 2, stride = (int64_t)gsize * 8, task0 = (int64_t)gidx * 8 + w;
+            if ((int64_t)gidx * 8 < ntask) {
+                f32x4 x[4][2];
+                if (task0 < ntask) gfix_apply_load_x<2>(X, rows, task0, l31, hi, x);
+                float tq[2][GfixApply<2, V5_THREADS>::NBLK][8];
+                gfix_apply_fetch<2, V5_THREADS, true>(a.gfix.Q + (int64_t)(1 - f) * 2 * K * K, tid, tq, redq);
+                __syncthreads();
+                float sq[2];
+                gfix_apply_planes<2, V5_THREADS>(qpl, tid, tq, redq, sq);
+                __syncthreads();
+                for (int64_t task = task0; task < ntask; task += stride) {
+                    if (task != task0) gfix_apply_load_x<2>(X, rows, task, l31, hi, x);
+                    gfix_apply_task<2>(rows, a.gfix.out[f], K, qpl, task, l31, hi, sc, sq, x);
+                }
+            }
+            if (f + 1 < fEnd) __syncthreads();       // (the planes are restaged)
         }
     }
     if constexpr (PROF) {
@@ -1029,20 +1136,27 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
 #undef PH
 }
 
-template <bool PROF, bool HASW, bool CHAIN, bool LOSS, bool R3 = false, bool HH = false, bool RS = false, bool ONLYS = false, bool Y16 = false>
+template <bool PROF, bool HASW, bool CHAIN, bool LOSS, bool R3 = false, bool HH = false, bool RS = false, bool ONLYS = false, bool Y16 = false, bool GF = false>
 static hipError_t grad_launch_f16_v8_t(const GradV4Args& a, hipStream_t stream) {
     constexpr int lds = R3 ? V7_LDS_BYTES : V8_LDS_BYTES;        // (three S terms: the split-bf16 kernel's 160 KB)
-    hipError_t e = hipFuncSetAttribute((const void*)k_grad_f16_v8<PROF, HASW, CHAIN, LOSS, R3, HH, RS, ONLYS, Y16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipError_t e = hipFuncSetAttribute((const void*)k_grad_f16_v8<PROF, HASW, CHAIN, LOSS, R3, HH, RS, ONLYS, Y16, GF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_grad_f16_v8<PROF, HASW, CHAIN, LOSS, R3, HH, RS, ONLYS, Y16>), dim3(a.gridX * a.gridY), dim3(V5_THREADS), lds, stream, a);
+    hipLaunchKernelGGL((k_grad_f16_v8<PROF, HASW, CHAIN, LOSS, R3, HH, RS, ONLYS, Y16, GF>), dim3(a.gridX * a.gridY), dim3(V5_THREADS), lds, stream, a);
     return hipGetLastError();
 }
 // inst (k1_instance): K1_HH, K1_R3 or K1_PLAIN
-static hipError_t grad_launch_f16_v8(const GradV4Args& a, K1Inst inst, hipStream_t stream) {
+static hipError_t grad_launch_f16_v8(const GradV4Args& a, K1Inst inst, hipStream_t stream, bool* rode = nullptr) {
     if (inst == K1_HH) {             // [r5] the high x high residual whose missing terms arrive as a correction slab
         const bool split = !(getenv("PMX_K1_ROLE_SPLIT") && atoi(getenv("PMX_K1_ROLE_SPLIT")) == 0);     // (PMX_K1_ROLE_SPLIT=0: A/B)
         // [r7] <Y16>: Y sixteen bytes per lane where its pitch and base allow it (PMX_K1_Y16=0: the 8-byte fetch, for A/B runs and the tests)
         const bool y16 = a.y16 && !a.prof && !(getenv("PMX_K1_Y16") && atoi(getenv("PMX_K1_Y16")) == 0);
+        // GF: the K x K correction rides in this launch (enqueue_grad_once armed it: GfixRide::seq) -- the <RS> instances only
+        const bool ride = a.gfix.seq != 0 && split && (a.doA & 1) && a.doS && !a.prof;
+        if (ride) {
+            if (rode) *rode = true;
+            if (y16) return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, false, true, true, false, true, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, false, true, true, false, true, true>(a, stream);
+            return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, false, true, true, false, false, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, false, true, true, false, false, true>(a, stream);
+        }
         if (y16) {
             if (split && (a.doA & 1) && a.doS)
                 return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, false, true, true, false, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, false, true, true, false, true>(a, stream);

@@ -138,6 +138,12 @@ struct pmx_ctx {
     float* fixQ = nullptr;                 // [2][2][Kk * Kk]
     float* fixSlab[2] = {nullptr, nullptr};   // the correction slabs (rowsK[j] x Kk)
     long long* fixProf = nullptr;          // PMX_GFIX_PROF=1: time stamps of the correction kernels' first workgroup (printed by pmx_time_grad)
+    unsigned* fixArrive = nullptr;         // k_grad_f16_v8<.., GF> (the correction riding in K1): arrival words [2][GFIX_RIDE_WGS], word = number of the launch that wrote it
+    unsigned fixSeq = 0;                   // ride launches so far (the next launch's number is fixSeq + 1)
+    bool gfix_ride_off = false;            // a ride reported K1_FAULT_GFIX: stand-alone correction launches for the rest of the context's life
+    bool gfix_ride_hold = false;           // pmx_time_grad: K1 alone is what it times
+    int hook_inject_gfix = 0;              // PMX_INJECT_GFIX_FAULT=n (tests; read once, at pmx_ctx_create): the n-th ride reports the ride's fault
+    int gfixRides = 0, gfixTriples = 0, gfixFaults = 0;    // pmx_gfix_info
     bool fix_on = false;                   // the last gradient pass ran an <HH> kernel: the update kernels fold fixSlab behind K1's slabs (slab_ref)
     bool k1_sync_check = false;            // one-iteration-per-call paths (nothing to repeat into): every fp16 K1 launch is awaited and, refused, repeated in fp32 on the spot (enqueue_grad)
     int ncu = 0;
@@ -472,6 +478,7 @@ extern "C" int pmx_ctx_create(pmx_ctx** out, int device, int64_t M, int64_t N, i
     }
     if (const char* e = getenv("PMX_GRAM_IN_UPDATE")) c->gram_in_update = atoi(e) != 0;
     if (const char* e = getenv("PMX_INJECT_K1_FAULT")) c->hook_inject_k1 = atoi(e);
+    if (const char* e = getenv("PMX_INJECT_GFIX_FAULT")) c->hook_inject_gfix = atoi(e);
     if (const char* e = getenv("PMX_FOLD_IN_K1")) c->fold_in_k1 = atoi(e) != 0;
     if (const char* e = getenv("PMX_TAIL_LOCKFILE")) c->hook_tail_lockfile = e;
     int ncu = 0;
@@ -562,6 +569,7 @@ extern "C" int pmx_ctx_create(pmx_ctx** out, int device, int64_t M, int64_t N, i
     if (rc == PMX_OK && k1_instance(c->k1, c->f16_r3, false, true, true) == K1_HH) {          // <HH> instances can run: the correction's matrices and slabs
         rc = dallocT(c, &c->fixPart, (size_t)2 * GFIX_PARTS * 2 * c->Kk * c->Kk, false);
         if (rc == PMX_OK) rc = dallocT(c, &c->fixQ, (size_t)4 * c->Kk * c->Kk);
+        if (rc == PMX_OK && c->k1 == K1_F16_V8) rc = dallocT(c, &c->fixArrive, (size_t)2 * GFIX_RIDE_WGS);
         for (int j = 0; j < 2 && rc == PMX_OK; ++j) rc = dallocT(c, &c->fixSlab[j], (size_t)c->rowsK[j] * c->Kk);
         if (rc == PMX_OK && getenv("PMX_GFIX_PROF")) rc = dallocT(c, &c->fixProf, 16);
     }
@@ -719,6 +727,15 @@ extern "C" int pmx_k1_info(pmx_ctx* c, int info[8]) {
     info[5] = c->plan.gridY;
     info[6] = c->plan.RP;
     info[7] = c->chainFaults + 1000 * c->tailFaults + (c->tail_fused ? 1000000 : 0) + 10000000 * std::min(c->rangeFaults, 9);
+    return PMX_OK;
+}
+
+extern "C" int pmx_gfix_info(pmx_ctx* c, int info[4]) {
+    if (!c || !info) FAIL(PMX_E_INVALID, "NULL argument");
+    info[0] = c->gfixRides;
+    info[1] = c->gfixTriples;
+    info[2] = c->gfix_ride_off ? 1 : 0;
+    info[3] = c->gfixFaults;
     return PMX_OK;
 }
 
@@ -1174,6 +1191,9 @@ static int chain_fault_fallback(pmx_ctx* c, int* again) {
     if (c->hstatus->k1_fault == 4) {
         rc = k1_leave_f16(c);
         if (rc != PMX_OK) return rc;
+    } else if (c->hstatus->k1_fault == K1_FAULT_GFIX) {     // the correction riding in K1 missed an arrival: the three stand-alone launches from here on
+        c->gfix_ride_off = true;
+        c->gfixFaults += 1;
     } else if (c->hstatus->k1_fault) {
         rc = chain_disable(c);
         if (rc != PMX_OK) return rc;
@@ -1328,6 +1348,7 @@ static int enqueue_grad_once(pmx_ctx* c, const float* A, const float* St, int do
     if (k1_fp16(c->k1) && !absmax_fresh) enqueue_absmax(c, A, St);      // (fresh: k_ada_finish left the maxima of these factors)
     K1Inst inst = K1_PLAIN;
     int rc = PMX_OK;
+    bool rode = false;                     // the launch carried the K x K correction (k_grad_f16_v8<.., GF>)
     switch (c->k1) {
     case K1_F16_K128: {
         SplitAArgs sp{};
@@ -1379,7 +1400,27 @@ static int enqueue_grad_once(pmx_ctx* c, const float* A, const float* St, int do
         }
         if (c->chainL > 0) rc = chain_arm(c, g);     // k_grad_f16_v8<.., CHAIN> / k_grad_bf16_v7<.., CHAIN>
         const bool v8 = c->k1 == K1_F16_V8 && inst != K1_V7;
-        if (rc == PMX_OK) rc = k1_timed(c, [&] { return v8 ? grad_launch_f16_v8(g, inst, c->stream) : grad_launch_bf16_v7(g, c->stream); });
+        // <.., GF>: the correction's three stages on this launch's idle waves instead of three launches behind it (k_gfix_dev.h).  Both gradients wanted
+        // (the <RS> instance), a path that can repeat the iteration after a fault, every region of the plan inside the matrix (an empty region returns before
+        // the stages), a context that has not fallen back; PMX_K1_GFIX=0: the stand-alone launches (A/B runs and the tests).  The region test cannot fail with
+        // today's planner (plan_row_regions: gridX = ceil(panels / RP), whole column regions) and no test reaches its other arm; it stands because the
+        // kernel's `T <= 0` return comes before the stages, and a planner that left a region empty would otherwise turn every launch into a 20 ms time-out.
+        // Armed only where grad_launch_f16_v8 picks the <.., GF> instance (role split on, no phase profile): GfixRide::seq counts rides, nothing else.
+        if (v8 && inst == K1_HH && rc == PMX_OK && (doA & 1) && doS && !c->k1_sync_check && !c->gfix_ride_off && !c->gfix_ride_hold && c->fixArrive != nullptr &&
+            !g.prof && !(getenv("PMX_K1_ROLE_SPLIT") && atoi(getenv("PMX_K1_ROLE_SPLIT")) == 0) &&
+            (int64_t)(c->plan.gridX - 1) * c->plan.RP * 128 < c->Mk && !(getenv("PMX_K1_GFIX") && atoi(getenv("PMX_K1_GFIX")) == 0)) {
+            if (c->fixSeq >= (1u << 30)) {       // (the words are compared for equality: start over long before the number wraps)
+                HIP_CHECK(hipMemsetAsync(c->fixArrive, 0, (size_t)2 * GFIX_RIDE_WGS * sizeof(unsigned), c->stream));
+                c->fixSeq = 0;
+            }
+            g.gfix.rows[0] = c->M; g.gfix.rows[1] = c->N;
+            g.gfix.part = c->fixPart; g.gfix.Q = c->fixQ;
+            g.gfix.out[0] = c->fixSlab[0]; g.gfix.out[1] = c->fixSlab[1];
+            g.gfix.arrive = c->fixArrive;
+            g.gfix.seq = ++c->fixSeq;
+            g.gfix.inject = c->hook_inject_gfix > 0 && (int)c->fixSeq == c->hook_inject_gfix;
+        }
+        if (rc == PMX_OK) rc = k1_timed(c, [&] { return v8 ? grad_launch_f16_v8(g, inst, c->stream, &rode) : grad_launch_bf16_v7(g, c->stream); });
         break;
     }
     case K1_BF16: {
@@ -1419,8 +1460,10 @@ static int enqueue_grad_once(pmx_ctx* c, const float* A, const float* St, int do
     if (grad) c->fix_on = inst == K1_HH;
     // what the high x high residual left out, as one more slab per block (k_gfix.hip).  In the launch stream: the three launches depend on the
     // factors only, but nothing fits BESIDE K1 (its waves hold all 512 registers of every SIMD) -- measured on a stream of their own they sat
-    // behind K1's workgroups and the pass got 2 % slower (profiles/r05_a_gfix_side_stream.txt)
-    if (inst == K1_HH) return enqueue_gfix(c, A, St, doA, doS, c->stream);
+    // behind K1's workgroups and the pass got 2 % slower (profiles/r05_a_gfix_side_stream.txt).  K1_F16_V8's two-gradient pass carries them itself, on
+    // waves that idle at both ends of the launch (rode: k_grad_f16_v8<.., GF>); every other route, and a context whose ride has faulted, launches them here.
+    if (rode) { c->gfixRides += 1; return PMX_OK; }
+    if (inst == K1_HH) { c->gfixTriples += 1; return enqueue_gfix(c, A, St, doA, doS, c->stream); }
     return PMX_OK;
 }
 
@@ -1804,7 +1847,11 @@ extern "C" int pmx_grad(pmx_ctx* c) {
         HIP_CHECK(hipStreamSynchronize(c->stream));
         return PMX_OK;
     }
-    for (int attempt = 0; attempt < 2; ++attempt) {
+    // One attempt per repairable fault class and one more: a refused range (k1_fault 4) leaves the fp16 kernels, a chain fault (1-3) the chains, the
+    // correction riding in K1 (5) the ride -- each can happen once per context, and two of them share a cause (workgroups not co-resident).  A pass
+    // that still faults after that is an error: the fold was skipped under the halt and G holds an older gradient.
+    bool clean = false;
+    for (int attempt = 0; attempt < 4 && !clean; ++attempt) {
         HIP_CHECK(hipMemsetAsync(&c->dstatus->halt, 0, sizeof(int), c->stream));
         rc = enqueue_grad(c, c->X[0], c->X[1], 1, 1);
         if (rc != PMX_OK) return rc;
@@ -1814,14 +1861,15 @@ extern "C" int pmx_grad(pmx_ctx* c) {
         f.status = c->dstatus;
         launch_fold(f, 2, c->stream);
         HIP_CHECK(hipGetLastError());
-        if (c->chainL == 0 && !k1_fp16(c->k1)) { HIP_CHECK(hipStreamSynchronize(c->stream)); break; }
+        if (c->chainL == 0 && !k1_fp16(c->k1)) { HIP_CHECK(hipStreamSynchronize(c->stream)); return PMX_OK; }
         rc = read_status(c);
         if (rc != PMX_OK) return rc;
         int again = 0;
         rc = chain_fault_fallback(c, &again);
         if (rc != PMX_OK) return rc;
-        if (!again) break;
+        clean = !again;
     }
+    if (!clean) FAIL(PMX_E_HIP, "pmx_grad: K1 reported a fault in every attempt (the last one with every fall-back taken); the gradient buffers were not written");
     return PMX_OK;
 }
 
@@ -1835,8 +1883,12 @@ extern "C" int pmx_time_grad(pmx_ctx* c, int do_A, int do_S, int reps, double* a
     }
     if (c->k1prof) HIP_CHECK(hipMemsetAsync(c->k1prof, 0, 16 * sizeof(unsigned long long), c->stream));
     HIP_CHECK(hipMemsetAsync(&c->dstatus->halt, 0, sizeof(int), c->stream));
-    const bool was = c->timing;
+    struct Restore {                       // (the HIP_CHECKs below return early: neither switch may stay flipped)
+        pmx_ctx* c; bool timing;
+        ~Restore() { c->timing = timing; c->gfix_ride_hold = false; }
+    } restore{c, c->timing};
     c->timing = false;
+    c->gfix_ride_hold = true;              // (nothing looks at DevStatus behind these launches: the correction stays on its stand-alone launches)
     rc = enqueue_grad(c, c->X[0], c->X[1], do_A, do_S);   // warm-up
     hipEvent_t e0, e1;
     HIP_CHECK(hipEventCreate(&e0));
@@ -1849,7 +1901,6 @@ extern "C" int pmx_time_grad(pmx_ctx* c, int do_A, int do_S, int reps, double* a
     HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    c->timing = was;
     *avg_ms = ms / reps;
     if (c->fixProf && c->fix_on) {
         long long h[16];

@@ -463,6 +463,13 @@ class DeviceNMF:
         d["frame_K"] = fr[2]                 # != K: K1 runs the next tuned K on zero-padded copies of the factors
         return d
 
+    def gfix_info(self):
+        """Who formed mode f16x2r's K x K correction in this context so far (include/pmx.h: pmx_gfix_info): K1 launches that carried it,
+        stand-alone triples of launches, and whether a carried correction faulted and the context fell back to the launches."""
+        v = (C.c_int * 4)()
+        _lib.check(self.lib.pmx_gfix_info(self.h, v))
+        return {"in_k1": v[0], "launches": v[1], "fell_back": bool(v[2]), "faults": v[3]}
+
     # -- single operations --------------------------------------------------------------------
     def grad(self):
         """nmf.grad_likelihood at the current device factors -> (gA (M x K), gS (K x N))."""
