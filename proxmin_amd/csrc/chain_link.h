@@ -15,7 +15,7 @@
 //     flushed()      after the wave's plain stores of the summed tile: the arrival k + 1 is pending ...
 //     publish()      ... and goes out at the top of the next panel behind s_waitcnt vmcnt(0) (the stores are in L2): relaxed agent-scope
 //                    store.  No release fence, no write-back: the lines stay dirty in the L2 the members share.
-// fault() reports through DevStatus (k1_fault, halt): the chain of kernels stops before anything is updated and the host repeats
+// fault() reports through DevStatus (k1_fault = a K1Fault, halt): the chain of kernels stops before anything is updated and the host repeats
 // the iteration with one slab per column region for the rest of the context's life (pmx_api.hip: chain_fault_fallback).
 // HIP promises neither the placement nor the co-residency this relies on for SPEED; correctness never assumes them.
 #pragma once
@@ -87,13 +87,13 @@ struct ChainLink {
             for (int spins = 1; (v >> 4) != cwant; ++spins) {
                 if ((spins & 63) == 0) {
                     if (chain_halted(status)) { fault(0); break; }              // somebody else gave up
-                    if (wall_clock64() - t0 > 2000000) { fault(1); break; }     // 20 ms
+                    if (wall_clock64() - t0 > 2000000) { fault(K1_FAULT_LATE); break; }     // 20 ms
                 }
                 __builtin_amdgcn_s_sleep(8);
                 v = __builtin_amdgcn_readfirstlane(__hip_atomic_load(curFlag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
             }
         }
-        if (cadd && (v & 15u) != myxcc) fault(2);
+        if (cadd && (v & 15u) != myxcc) fault(K1_FAULT_XCD);
         asm volatile("" ::: "memory");   // the sc1 loads of the previous sum stay behind the arrival check
     }
     __device__ __forceinline__ void flushed() {

@@ -369,7 +369,6 @@ __device__ __forceinline__ int gfix_ride_tid() {
     asm volatile("" : "+v"(t));
     return t;
 }
-constexpr int K1_FAULT_GFIX = 5;         // DevStatus::k1_fault: a stage of the ride did not arrive in time (the host falls back to the stand-alone launches)
 
 // all of the first n (<= GFIX_RIDE_WGS) words equal seq?  One wave; uniform result.
 __device__ __forceinline__ bool gfix_ride_arrived(const unsigned* words, int n, unsigned seq, int lane) {

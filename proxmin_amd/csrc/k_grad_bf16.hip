@@ -868,7 +868,7 @@ struct GradV4Args {
     unsigned chainBase;  // launch sequence number * 64
     DevStatus* wstatus;  // writable view of `status` (fault report)
     int chainInject;     // tests: report a fault from this launch (exercises the host's fall-back)
-    float rangeRatio;    // [r4] two-term fp16 kernels: report k1_fault 4 when K max|A| max|S| > rangeRatio max|Y| (0: no check; f16_range_fault)
+    float rangeRatio;    // [r4] two-term fp16 kernels: report K1_FAULT_RANGE when K max|A| max|S| > rangeRatio max|Y| (0: no check; f16_range_fault)
     int r3;              // [r4] k_grad_f16_v8<.., R3>: third terms of A and S in the residual's product, two accumulators
     int consPrio;        // [r6] s_setprio level of the CONSUMER waves for the launch (0: none): the consumers are the pole of every slot, the producers wait ~30 % of it at the barrier
     K1GramFold fold;     // [r6] k_grad_f16_k32: the step rule's Gram fold riding in the first workgroups (pmx_common.h)
@@ -1232,7 +1232,7 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_bf16_v7(GradV4Args a) {
         ChainLink link;                      // chain_link.h: the hand-off protocol
         if constexpr (CHAIN) link.init(a.chainFlags, chainId, nrp, j, a.status, a.wstatus, lane);
         if constexpr (CHAIN) {
-            if (a.chainInject && blockIdx.x == 0 && j == 0) link.fault(3);
+            if (a.chainInject && blockIdx.x == 0 && j == 0) link.fault(K1_FAULT_INJECTED);
         }
         auto consume = [&](int b, int prow, int cb, f32x16& accSc) {     // block b: column block cb of the panel at row prow
             const unsigned char* Rb = smem + V7_OFF_R + (b & 1) * V5_R_BYTES;
@@ -1381,17 +1381,22 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_bf16_v7(GradV4Args a) {
 #undef PH
 }
 
-template <bool PROF, bool HASW, bool CHAIN>
+// F: the instance as its V7_* flags (k1_instance.h)
+template <unsigned F>
 static hipError_t grad_launch_bf16_v7_t(const GradV4Args& a, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_grad_bf16_v7<PROF, HASW, CHAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, V7_LDS_BYTES);
+    constexpr auto kernel = k_grad_bf16_v7<(F & V7_PROF) != 0, (F & V7_HASW) != 0, (F & V7_CHAIN) != 0>;
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, V7_LDS_BYTES);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_grad_bf16_v7<PROF, HASW, CHAIN>), dim3(a.gridX * a.gridY), dim3(V5_THREADS), V7_LDS_BYTES, stream, a);
+    hipLaunchKernelGGL(kernel, dim3(a.gridX * a.gridY), dim3(V5_THREADS), V7_LDS_BYTES, stream, a);
     return hipGetLastError();
 }
-static hipError_t grad_launch_bf16_v7(const GradV4Args& a, hipStream_t stream) {
-    if (a.chainL > 0) return a.W != nullptr ? grad_launch_bf16_v7_t<false, true, true>(a, stream) : grad_launch_bf16_v7_t<false, false, true>(a, stream);
-    if (a.W != nullptr) return grad_launch_bf16_v7_t<false, true, false>(a, stream);   // (no phase profiling of the weighted instance)
-    return a.prof ? grad_launch_bf16_v7_t<true, false, false>(a, stream) : grad_launch_bf16_v7_t<false, false, false>(a, stream);
+// flags: k1_flags_bf16_v7's answer for this launch; the instances that exist are K1_BF16_V7_INSTANCES
+static hipError_t grad_launch_bf16_v7(const GradV4Args& a, unsigned flags, hipStream_t stream) {
+#define K1_LAUNCHER(F) grad_launch_bf16_v7_t<(F)>,
+    static constexpr hipError_t (*launch[])(const GradV4Args&, hipStream_t) = {K1_BF16_V7_INSTANCES(K1_LAUNCHER)};
+#undef K1_LAUNCHER
+    const int i = k1_find_instance(K1_BF16_V7_KEYS, flags);
+    return i < 0 ? hipErrorInvalidValue : launch[i](a, stream);
 }
 
 // k_grad_f16_v8 (two-term fp16 split, the shipped K = 64 kernel of mode f16x2) lives in its own file

@@ -449,17 +449,21 @@ GradPlan grad_plan_f16_k32(int64_t M, int64_t N) {
     p.ldsBytes = V8_LDS_BYTES;
     return p;
 }
-template <bool LOSS, bool R3 = false>
+// F: the instance as its K32_* flags (k1_instance.h)
+template <unsigned F>
 static hipError_t grad_launch_f16_k32_t(const GradV4Args& a, hipStream_t stream) {
-    constexpr int lds = R3 ? V7_LDS_BYTES : V8_LDS_BYTES;
-    hipError_t e = hipFuncSetAttribute((const void*)k_grad_f16_k32<LOSS, R3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    constexpr auto kernel = k_grad_f16_k32<(F & K32_LOSS) != 0, (F & K32_R3) != 0>;
+    constexpr int lds = (F & K32_R3) ? V7_LDS_BYTES : V8_LDS_BYTES;
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_grad_f16_k32<LOSS, R3>), dim3(a.gridX * a.gridY), dim3(V5_THREADS), lds, stream, a);
+    hipLaunchKernelGGL(kernel, dim3(a.gridX * a.gridY), dim3(V5_THREADS), lds, stream, a);
     return hipGetLastError();
 }
-// inst (k1_instance): K1_R3 or K1_PLAIN
-hipError_t grad_launch_f16_k32(const GradV4Args& a, K1Inst inst, hipStream_t stream) {
-    if (inst == K1_R3) return (!(a.doA & 1) && !a.doS) ? grad_launch_f16_k32_t<true, true>(a, stream) : grad_launch_f16_k32_t<false, true>(a, stream);
-    if (!(a.doA & 1) && !a.doS) return grad_launch_f16_k32_t<true>(a, stream);      // the loss-only pass (pmx_loglike, the line search)
-    return grad_launch_f16_k32_t<false>(a, stream);
+// flags: k1_flags_f16_k32's answer for this launch; the instances that exist are K1_F16_K32_INSTANCES
+hipError_t grad_launch_f16_k32(const GradV4Args& a, unsigned flags, hipStream_t stream) {
+#define K1_LAUNCHER(F) grad_launch_f16_k32_t<(F)>,
+    static constexpr hipError_t (*launch[])(const GradV4Args&, hipStream_t) = {K1_F16_K32_INSTANCES(K1_LAUNCHER)};
+#undef K1_LAUNCHER
+    const int i = k1_find_instance(K1_F16_K32_KEYS, flags);
+    return i < 0 ? hipErrorInvalidValue : launch[i](a, stream);
 }

@@ -51,13 +51,13 @@ __device__ __forceinline__ f16x8 v8_tr_pair(const unsigned char* base, int off0,
 // with P = 0 (rows of A / columns of S the prox has set to zero: R = -Y there, and the whole gradient of such a row comes from
 // them) fall below that.  fp32 carries an exponent per entry and does not care.  The kernels therefore refuse to run when
 // K max|A| max|S| > ratio * max|Y| (ratio 2^16: R = -Y entries down to 2^-8 max|Y| keep both terms): every workgroup returns
-// before anything is written, workgroup 0 reports DevStatus::k1_fault = 4 and halts the chain of kernels; the host continues
+// before anything is written, workgroup 0 reports DevStatus::k1_fault = K1_FAULT_RANGE and halts the chain of kernels; the host continues
 // the SAME iteration with the exact-fp32 kernel of the frame for the rest of the context's life (pmx_api.hip: k1_leave_f16).
 // Gradient passes only: the loss-only instance sums fp32 residuals before the split.  Uniform over the grid (same inputs).
 __device__ __forceinline__ bool f16_range_fault(float boundP, float ymax, float ratio, int doA, int doS, DevStatus* wst, int tid) {
     if (!(ratio > 0.f) || wst == nullptr || !(doA | doS) || !(ymax > 0.f) || !(boundP > ratio * ymax)) return false;
     if (blockIdx.x == 0 && tid == 0) {
-        wst->k1_fault = 4;
+        wst->k1_fault = K1_FAULT_RANGE;
         wst->reason = HALT_ERROR;
         __threadfence();
         wst->halt = 1;
@@ -700,7 +700,7 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
             ChainLink link;
             if constexpr (CHAIN) link.init(a.chainFlags, chainId, nrp, j, a.status, a.wstatus, lane);
             if constexpr (CHAIN) {
-                if (a.chainInject && blockIdx.x == 0 && j == 0) link.fault(3);
+                if (a.chainInject && blockIdx.x == 0 && j == 0) link.fault(K1_FAULT_INJECTED);
             }
             sync();
             if constexpr (GF) {
@@ -967,7 +967,7 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
         ChainLink link;
         if constexpr (CHAIN) link.init(a.chainFlags, chainId, nrp, j, a.status, a.wstatus, lane);
         if constexpr (CHAIN) {
-            if (a.chainInject && blockIdx.x == 0 && j == 0) link.fault(3);
+            if (a.chainInject && blockIdx.x == 0 && j == 0) link.fault(K1_FAULT_INJECTED);
         }
         sync();
         sync();
@@ -1136,47 +1136,23 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_v8(GradV4Args a) {
 #undef PH
 }
 
-template <bool PROF, bool HASW, bool CHAIN, bool LOSS, bool R3 = false, bool HH = false, bool RS = false, bool ONLYS = false, bool Y16 = false, bool GF = false>
+// F: the instance as its V8_* flags (k1_instance.h)
+template <unsigned F>
 static hipError_t grad_launch_f16_v8_t(const GradV4Args& a, hipStream_t stream) {
-    constexpr int lds = R3 ? V7_LDS_BYTES : V8_LDS_BYTES;        // (three S terms: the split-bf16 kernel's 160 KB)
-    hipError_t e = hipFuncSetAttribute((const void*)k_grad_f16_v8<PROF, HASW, CHAIN, LOSS, R3, HH, RS, ONLYS, Y16, GF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    constexpr auto kernel = k_grad_f16_v8<(F & V8_PROF) != 0, (F & V8_HASW) != 0, (F & V8_CHAIN) != 0, (F & V8_LOSS) != 0, (F & V8_R3) != 0, (F & V8_HH) != 0,
+                                          (F & V8_RS) != 0, (F & V8_ONLYS) != 0, (F & V8_Y16) != 0, (F & V8_GF) != 0>;
+    constexpr int lds = (F & V8_R3) ? V7_LDS_BYTES : V8_LDS_BYTES;        // (three S terms: the split-bf16 kernel's 160 KB)
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_grad_f16_v8<PROF, HASW, CHAIN, LOSS, R3, HH, RS, ONLYS, Y16, GF>), dim3(a.gridX * a.gridY), dim3(V5_THREADS), lds, stream, a);
+    hipLaunchKernelGGL(kernel, dim3(a.gridX * a.gridY), dim3(V5_THREADS), lds, stream, a);
     return hipGetLastError();
 }
-// inst (k1_instance): K1_HH, K1_R3 or K1_PLAIN
-static hipError_t grad_launch_f16_v8(const GradV4Args& a, K1Inst inst, hipStream_t stream, bool* rode = nullptr) {
-    if (inst == K1_HH) {             // [r5] the high x high residual whose missing terms arrive as a correction slab
-        const bool split = !(getenv("PMX_K1_ROLE_SPLIT") && atoi(getenv("PMX_K1_ROLE_SPLIT")) == 0);     // (PMX_K1_ROLE_SPLIT=0: A/B)
-        // [r7] <Y16>: Y sixteen bytes per lane where its pitch and base allow it (PMX_K1_Y16=0: the 8-byte fetch, for A/B runs and the tests)
-        const bool y16 = a.y16 && !a.prof && !(getenv("PMX_K1_Y16") && atoi(getenv("PMX_K1_Y16")) == 0);
-        // GF: the K x K correction rides in this launch (enqueue_grad_once armed it: GfixRide::seq) -- the <RS> instances only
-        const bool ride = a.gfix.seq != 0 && split && (a.doA & 1) && a.doS && !a.prof;
-        if (ride) {
-            if (rode) *rode = true;
-            if (y16) return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, false, true, true, false, true, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, false, true, true, false, true, true>(a, stream);
-            return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, false, true, true, false, false, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, false, true, true, false, false, true>(a, stream);
-        }
-        if (y16) {
-            if (split && (a.doA & 1) && a.doS)
-                return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, false, true, true, false, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, false, true, true, false, true>(a, stream);
-            if (split && !(a.doA & 1) && a.doS)
-                return grad_launch_f16_v8_t<false, false, false, false, false, true, false, true, true>(a, stream);
-            return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, false, true, false, false, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, false, true, false, false, true>(a, stream);
-        }
-        if (split && (a.doA & 1) && a.doS && !a.prof)   // <RS>: both gradients wanted
-            return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, false, true, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, false, true, true>(a, stream);
-        if (split && !(a.doA & 1) && a.doS)             // <ONLYS>: gSt alone
-            return grad_launch_f16_v8_t<false, false, false, false, false, true, false, true>(a, stream);
-        return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, false, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, false, true>(a, stream);
-    }
-    if (inst == K1_R3) {             // the residual to fp32's class
-        if (!(a.doA & 1) && !a.doS) return grad_launch_f16_v8_t<false, false, false, true, true>(a, stream);
-        return a.chainL > 0 ? grad_launch_f16_v8_t<false, false, true, false, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, false, true>(a, stream);
-    }
-    if (!(a.doA & 1) && !a.doS)      // the loss-only pass (no gradient is written: nothing to chain)
-        return a.W != nullptr ? grad_launch_f16_v8_t<false, true, false, true>(a, stream) : grad_launch_f16_v8_t<false, false, false, true>(a, stream);
-    if (a.chainL > 0) return a.W != nullptr ? grad_launch_f16_v8_t<false, true, true, false>(a, stream) : grad_launch_f16_v8_t<false, false, true, false>(a, stream);
-    if (a.W != nullptr) return grad_launch_f16_v8_t<false, true, false, false>(a, stream);   // (no phase profiling of the weighted instance)
-    return a.prof ? grad_launch_f16_v8_t<true, false, false, false>(a, stream) : grad_launch_f16_v8_t<false, false, false, false>(a, stream);
+// flags: k1_flags_f16_v8's answer for this launch; the instances that exist are K1_F16_V8_INSTANCES
+static hipError_t grad_launch_f16_v8(const GradV4Args& a, unsigned flags, hipStream_t stream) {
+#define K1_LAUNCHER(F) grad_launch_f16_v8_t<(F)>,
+    static constexpr hipError_t (*launch[])(const GradV4Args&, hipStream_t) = {K1_F16_V8_INSTANCES(K1_LAUNCHER)};
+#undef K1_LAUNCHER
+    const int i = k1_find_instance(K1_F16_V8_KEYS, flags);
+    return i < 0 ? hipErrorInvalidValue : launch[i](a, stream);
 }
+

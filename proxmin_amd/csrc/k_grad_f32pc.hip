@@ -265,7 +265,7 @@ __global__ __launch_bounds__(512, 2) void k_grad_f32_pc(GradArgs a, int gridX, i
         ChainLink link;                      // chain_link.h: the hand-off protocol
         if constexpr (CHAIN) link.init(a.chainFlags, chainId, nrp, j, a.status, a.wstatus, lane);
         if constexpr (CHAIN) {
-            if (a.chainInject && blockIdx.x == 0 && j == 0) link.fault(3);
+            if (a.chainInject && blockIdx.x == 0 && j == 0) link.fault(K1_FAULT_INJECTED);
         }
         auto sync = [&]() {
             __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -422,19 +422,20 @@ GradPlan grad_plan_f32pc(int64_t M, int64_t N, int64_t K) {
     p.variant = -2;
     return p;
 }
-template <int K, bool HASW, bool CHAIN>
+// F: the instance as its PC_* flags (k1_instance.h)
+template <unsigned F>
 static hipError_t grad_launch_f32pc_t(const GradPlan& p, const GradArgs& a, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_grad_f32_pc<K, HASW, CHAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.ldsBytes);
+    constexpr auto kernel = k_grad_f32_pc<(F & PC_K64) ? 64 : 32, (F & PC_HASW) != 0, (F & PC_CHAIN) != 0>;
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.ldsBytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_grad_f32_pc<K, HASW, CHAIN>), dim3(p.gridX * p.gridY), dim3(512), p.ldsBytes, stream, a, p.gridX, p.gridY);
+    hipLaunchKernelGGL(kernel, dim3(p.gridX * p.gridY), dim3(512), p.ldsBytes, stream, a, p.gridX, p.gridY);
     return hipGetLastError();
 }
-template <int K>
-static hipError_t grad_launch_f32pc_k(const GradPlan& p, const GradArgs& a, hipStream_t stream) {
-    const bool w = a.W != nullptr;
-    if (a.chainL > 0) return w ? grad_launch_f32pc_t<K, true, true>(p, a, stream) : grad_launch_f32pc_t<K, false, true>(p, a, stream);
-    return w ? grad_launch_f32pc_t<K, true, false>(p, a, stream) : grad_launch_f32pc_t<K, false, false>(p, a, stream);
-}
-hipError_t grad_launch_f32pc(const GradPlan& p, const GradArgs& a, hipStream_t stream) {
-    return a.K == 64 ? grad_launch_f32pc_k<64>(p, a, stream) : grad_launch_f32pc_k<32>(p, a, stream);
+// flags: k1_flags_f32_pc's answer for this launch; the instances that exist are K1_F32_PC_INSTANCES
+hipError_t grad_launch_f32pc(const GradPlan& p, const GradArgs& a, unsigned flags, hipStream_t stream) {
+#define K1_LAUNCHER(F) grad_launch_f32pc_t<(F)>,
+    static constexpr hipError_t (*launch[])(const GradPlan&, const GradArgs&, hipStream_t) = {K1_F32_PC_INSTANCES(K1_LAUNCHER)};
+#undef K1_LAUNCHER
+    const int i = k1_find_instance(K1_F32_PC_KEYS, flags);
+    return i < 0 ? hipErrorInvalidValue : launch[i](p, a, stream);
 }

@@ -513,7 +513,7 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_k128(GradK128Args a)
                 }
             };
             if constexpr (CHAIN) {
-                if (a.chainInject && blockIdx.x == 0 && j == 0) link.fault(3);
+                if (a.chainInject && blockIdx.x == 0 && j == 0) link.fault(K1_FAULT_INJECTED);
             }
             sync();
             sync();
@@ -750,7 +750,7 @@ __global__ __launch_bounds__(V5_THREADS, 2) void k_grad_f16_k128(GradK128Args a)
             }
         };
         if constexpr (CHAIN) {
-            if (a.chainInject && blockIdx.x == 0 && j == 0) link.fault(3);
+            if (a.chainInject && blockIdx.x == 0 && j == 0) link.fault(K1_FAULT_INJECTED);
         }
         using c0 = std::integral_constant<int, 0>; using c1 = std::integral_constant<int, 1>;
         using c2 = std::integral_constant<int, 2>; using c3 = std::integral_constant<int, 3>;
@@ -845,21 +845,20 @@ GradPlan grad_plan_k128(int64_t M, int64_t N) {
     p.ldsBytes = W8_LDS_BYTES;
     return p;
 }
-template <bool HASW, bool CHAIN, bool HH = false, bool RS = false>
+// F: the instance as its K128_* flags (k1_instance.h)
+template <unsigned F>
 static hipError_t grad_launch_k128_t(const GradK128Args& a, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_grad_f16_k128<HASW, CHAIN, HH, RS>, hipFuncAttributeMaxDynamicSharedMemorySize, W8_LDS_BYTES);
+    constexpr auto kernel = k_grad_f16_k128<(F & K128_HASW) != 0, (F & K128_CHAIN) != 0, (F & K128_HH) != 0, (F & K128_RS) != 0>;
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, W8_LDS_BYTES);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_grad_f16_k128<HASW, CHAIN, HH, RS>), dim3(a.gridX * a.gridY), dim3(V5_THREADS), W8_LDS_BYTES, stream, a);
+    hipLaunchKernelGGL(kernel, dim3(a.gridX * a.gridY), dim3(V5_THREADS), W8_LDS_BYTES, stream, a);
     return hipGetLastError();
 }
-// inst (k1_instance): K1_HH or K1_PLAIN
-hipError_t grad_launch_k128(const GradK128Args& a, K1Inst inst, hipStream_t stream) {
-    if (inst == K1_HH) {
-        if ((a.doA & 1) && a.doS && !(getenv("PMX_K1_ROLE_SPLIT") && atoi(getenv("PMX_K1_ROLE_SPLIT")) == 0))    // <RS>: both gradients wanted (PMX_K1_ROLE_SPLIT=0: A/B)
-            return a.chainL > 0 ? grad_launch_k128_t<false, true, true, true>(a, stream) : grad_launch_k128_t<false, false, true, true>(a, stream);
-        return a.chainL > 0 && (a.doA & 1) ? grad_launch_k128_t<false, true, true>(a, stream) : grad_launch_k128_t<false, false, true>(a, stream);
-    }
-    if (a.chainL > 0 && (a.doA & 1))
-        return a.W != nullptr ? grad_launch_k128_t<true, true>(a, stream) : grad_launch_k128_t<false, true>(a, stream);
-    return a.W != nullptr ? grad_launch_k128_t<true, false>(a, stream) : grad_launch_k128_t<false, false>(a, stream);
+// flags: k1_flags_f16_k128's answer for this launch; the instances that exist are K1_F16_K128_INSTANCES
+hipError_t grad_launch_k128(const GradK128Args& a, unsigned flags, hipStream_t stream) {
+#define K1_LAUNCHER(F) grad_launch_k128_t<(F)>,
+    static constexpr hipError_t (*launch[])(const GradK128Args&, hipStream_t) = {K1_F16_K128_INSTANCES(K1_LAUNCHER)};
+#undef K1_LAUNCHER
+    const int i = k1_find_instance(K1_F16_K128_KEYS, flags);
+    return i < 0 ? hipErrorInvalidValue : launch[i](a, stream);
 }

@@ -176,7 +176,7 @@ struct pmx_ctx {
     int nSlabA = 0;                        // gA slabs the update kernels fold (plan.nSlabA, or one per chain group)
     int nSlabS = 0;                        // gSt slabs
     int chainFaults = 0;                   // times the chained mode was left after a fault
-    // test hooks, read from the environment ONCE when the context is created (never on a launch path):
+    // test hooks, read from the environment ONCE when the context is created (never on a launch path; K1's three A/B switches are read per launch, by k1_read_switches alone):
     int hook_inject_k1 = 0;                //   PMX_INJECT_K1_FAULT=n: the n-th chained K1 launch reports a fault
     std::string hook_tail_lockfile;        //   PMX_TAIL_LOCKFILE: several processes on ONE GPU take turns with the persistent tail
     bool tail_fused = false;               // adaprox: the iteration tail runs as one persistent kernel (k_ada_tail)
@@ -1124,7 +1124,7 @@ static int reset_status(pmx_ctx* c) {
 
 // what to tell the caller when a chain stopped with HALT_ERROR on a path that cannot repeat the iteration (one iteration per call)
 static const char* chain_error_text(pmx_ctx* c) {
-    if (c->hstatus && c->hstatus->k1_fault == 4)
+    if (c->hstatus && c->hstatus->k1_fault == K1_FAULT_RANGE)
         return "mode f16x2: K max|A| max|S| is more than 2^16 max|Y| -- one fp16 scale cannot carry this residual (f16_range_fault); create the context with PMX_MODE_F32";
     return "device chain reported an error";
 }
@@ -1154,7 +1154,7 @@ static int one_iteration_per_call(pmx_ctx* c) {
     c->k1_sync_check = true;
     return chain_disable(c);
 }
-// DevStatus::k1_fault == 4 (f16_range_fault, k_grad_f16_v8.hip): the two-term fp16 K1 refused a launch because one power-of-two
+// DevStatus::k1_fault == K1_FAULT_RANGE (f16_range_fault, k_grad_f16_v8.hip): the two-term fp16 K1 refused a launch because one power-of-two
 // scale cannot carry this residual.  Leave the fp16 kernels for good: the exact-fp32 K1 of the SAME frame (k_grad_f32_pc at
 // K1's K = 32 / 64, k_grad_f32<128> else; zero-padded Y / factor copies stay as they are), with its own grid, slabs, loss
 // partials and chain words.  The buffers of the fp16 plan stay allocated until the context is destroyed.
@@ -1188,13 +1188,13 @@ static int chain_fault_fallback(pmx_ctx* c, int* again) {
     if (c->hstatus->tail_fault == 2)         // a barrier inside the fused tail never completed: the iteration is half applied
         FAIL(PMX_E_HIP, "k_ada_tail: a grid barrier timed out after the census had passed (a workgroup was lost); the factors are not usable");
     int rc = PMX_OK;
-    if (c->hstatus->k1_fault == 4) {
+    if (c->hstatus->k1_fault == K1_FAULT_RANGE) {
         rc = k1_leave_f16(c);
         if (rc != PMX_OK) return rc;
     } else if (c->hstatus->k1_fault == K1_FAULT_GFIX) {     // the correction riding in K1 missed an arrival: the three stand-alone launches from here on
         c->gfix_ride_off = true;
         c->gfixFaults += 1;
-    } else if (c->hstatus->k1_fault) {
+    } else if (c->hstatus->k1_fault) {                      // K1_FAULT_LATE, _XCD, _INJECTED: the chains' hand-off does not hold here
         rc = chain_disable(c);
         if (rc != PMX_OK) return rc;
         c->chainFaults += 1;
@@ -1223,17 +1223,24 @@ static int chain_fault_fallback(pmx_ctx* c, int* again) {
     return PMX_OK;
 }
 
-static GradArgs small_grad_args(pmx_ctx* c, const float* A, const float* St, int doA, int doS) {
-    GradArgs g{};
+// what every K1 argument block holds, set by name (GradArgs, GradV4Args, GradK128Args, GradBfArgs: kernel ABI each, no common base)
+template <class Args>
+static Args k1_common_args(pmx_ctx* c, int doA, int doS) {
+    Args g{};
     g.Y = c->Y; g.ldY = c->ldY;
-    g.W = c->W; g.ldW = c->ldW;
-    g.A = A; g.St = St;
     g.slabA = c->slab[0]; g.slabS = c->slab[1];
     g.lossPart = c->lossPart;
     g.status = c->dstatus;
-    g.M = (int)c->Mk; g.N = (int)c->Nk; g.K = (int)c->Kk;
+    g.M = (int)c->Mk; g.N = (int)c->Nk;
     g.RP = c->plan.RP;
     g.doA = doA; g.doS = doS;
+    return g;
+}
+static GradArgs small_grad_args(pmx_ctx* c, const float* A, const float* St, int doA, int doS) {
+    GradArgs g = k1_common_args<GradArgs>(c, doA, doS);
+    g.W = c->W; g.ldW = c->ldW;
+    g.A = A; g.St = St;
+    g.K = (int)c->Kk;
     return g;
 }
 static bool eig_small_applies(const pmx_ctx* c) { return c->K <= 16 && c->M <= 8192 && c->N <= 8192; }
@@ -1304,15 +1311,8 @@ static int k1_timed(pmx_ctx* c, Launch&& launch) {
     return PMX_OK;
 }
 static GradV4Args v4_args(pmx_ctx* c, const float* A, const float* St, int doA, int doS) {
-    GradV4Args g{};
-    g.Y = c->Y; g.ldY = c->ldY;
+    GradV4Args g = k1_common_args<GradV4Args>(c, doA, doS);
     g.A = A; g.St = St;
-    g.slabA = c->slab[0]; g.slabS = c->slab[1];
-    g.lossPart = c->lossPart;
-    g.status = c->dstatus;
-    g.M = (int)c->Mk; g.N = (int)c->Nk;
-    g.RP = c->plan.RP;
-    g.doA = doA; g.doS = doS;
     g.gridX = c->plan.gridX; g.gridY = c->plan.gridY;
     return g;
 }
@@ -1346,23 +1346,19 @@ static int enqueue_grad_once(pmx_ctx* c, const float* A, const float* St, int do
     }
     const bool grad = (doA & 1) || doS;
     if (k1_fp16(c->k1) && !absmax_fresh) enqueue_absmax(c, A, St);      // (fresh: k_ada_finish left the maxima of these factors)
-    K1Inst inst = K1_PLAIN;
+    // What the choice of instance looks at (k1_instance.h): each tuned family completes the facts, asks its k1_flags_* ONCE, arms what the decided
+    // instance needs and hands the flags to its launcher.  inst stays K1_PLAIN in the families that have one instance per fact.
+    K1Facts facts{};
+    facts.doA = (doA & 1) != 0; facts.doS = doS != 0; facts.hasW = c->W != nullptr;
     int rc = PMX_OK;
-    bool rode = false;                     // the launch carried the K x K correction (k_grad_f16_v8<.., GF>)
+    bool rides = false;                    // the launch carries the K x K correction (k_grad_f16_v8<.., GF>)
     switch (c->k1) {
     case K1_F16_K128: {
         SplitAArgs sp{};
         sp.X = A; sp.count = c->M * c->Kk; /* (a frame's extra rows stay zero) */ sp.absmax = c->absmax; sp.H = c->A16[0]; sp.L = c->A16[1]; sp.status = c->dstatus;
         launch_split_a_f16(sp, c->stream);
-        GradK128Args g{};
-        g.Y = c->Y; g.ldY = c->ldY;
+        GradK128Args g = k1_common_args<GradK128Args>(c, doA, doS);
         g.Ah = c->A16[0]; g.Al = c->A16[1]; g.St = St;
-        g.slabA = c->slab[0]; g.slabS = c->slab[1];
-        g.lossPart = c->lossPart;
-        g.status = c->dstatus;
-        g.M = (int)c->Mk; g.N = (int)c->Nk;
-        g.RP = c->plan.RP;
-        g.doA = doA; g.doS = doS;
         g.gridX = c->plan.gridX; g.gridY = c->plan.gridY;
         g.absmax = c->absmax; g.ymax = c->ymax;
         g.W = c->W; g.ldW = c->ldW; g.wmax = c->wmax;
@@ -1371,18 +1367,20 @@ static int enqueue_grad_once(pmx_ctx* c, const float* A, const float* St, int do
             g.chainStride = 1;               // panels between neighbouring members' rotations (1 beats 2: profiles/r04_a_k128_chain_ab.txt)
             rc = chain_arm(c, g);
         }
-        inst = k1_instance(c->k1, c->f16_r3, c->W != nullptr, grad, true);
-        g.hh = inst == K1_HH;
+        facts.inst = k1_instance(c->k1, c->f16_r3, facts.hasW, grad, true);
+        facts.chain = g.chainL > 0;
+        g.hh = facts.inst == K1_HH;
         g.consPrio = k1_prio_for(128);
-        if (rc == PMX_OK) rc = k1_timed(c, [&] { return grad_launch_k128(g, inst, c->stream); });
+        const unsigned flags = k1_flags_f16_k128(facts, k1_read_switches());
+        if (rc == PMX_OK) rc = k1_timed(c, [&] { return grad_launch_k128(g, flags, c->stream); });
         break;
     }
     case K1_F16_K32: {
         GradV4Args g = v4_args(c, A, St, doA, doS);
         v4_f16_args(c, g, 32);
         g.fold = fold;
-        inst = k1_instance(c->k1, c->f16_r3, false, grad, true);
-        rc = k1_timed(c, [&] { return grad_launch_f16_k32(g, inst, c->stream); });
+        facts.inst = k1_instance(c->k1, c->f16_r3, false, grad, true);
+        rc = k1_timed(c, [&] { return grad_launch_f16_k32(g, k1_flags_f16_k32(facts), c->stream); });
         break;
     }
     case K1_F16_V8:
@@ -1395,20 +1393,27 @@ static int enqueue_grad_once(pmx_ctx* c, const float* A, const float* St, int do
             // its producers fetch Y (and W) eight bytes at a time: even pitch, 8-byte-aligned base, W at Y's pitch (its per-lane offsets);
             // anything else runs k_grad_bf16_v7 on the same frame
             c->k1_pairs = (c->ldY % 2) == 0 && (((uintptr_t)c->Y) & 7) == 0 && (c->W == nullptr || (c->ldW == c->ldY && (((uintptr_t)c->W) & 7) == 0));
-            inst = k1_instance(c->k1, c->f16_r3, c->W != nullptr, grad, c->k1_pairs);
+            facts.inst = k1_instance(c->k1, c->f16_r3, facts.hasW, grad, c->k1_pairs);
             g.y16 = c->k1_pairs && (c->ldY % 4) == 0 && (((uintptr_t)c->Y) & 15) == 0;     // the <HH> instances then fetch sixteen bytes per lane
         }
         if (c->chainL > 0) rc = chain_arm(c, g);     // k_grad_f16_v8<.., CHAIN> / k_grad_bf16_v7<.., CHAIN>
-        const bool v8 = c->k1 == K1_F16_V8 && inst != K1_V7;
-        // <.., GF>: the correction's three stages on this launch's idle waves instead of three launches behind it (k_gfix_dev.h).  Both gradients wanted
-        // (the <RS> instance), a path that can repeat the iteration after a fault, every region of the plan inside the matrix (an empty region returns before
-        // the stages), a context that has not fallen back; PMX_K1_GFIX=0: the stand-alone launches (A/B runs and the tests).  The region test cannot fail with
-        // today's planner (plan_row_regions: gridX = ceil(panels / RP), whole column regions) and no test reaches its other arm; it stands because the
-        // kernel's `T <= 0` return comes before the stages, and a planner that left a region empty would otherwise turn every launch into a 20 ms time-out.
-        // Armed only where grad_launch_f16_v8 picks the <.., GF> instance (role split on, no phase profile): GfixRide::seq counts rides, nothing else.
-        if (v8 && inst == K1_HH && rc == PMX_OK && (doA & 1) && doS && !c->k1_sync_check && !c->gfix_ride_off && !c->gfix_ride_hold && c->fixArrive != nullptr &&
-            !g.prof && !(getenv("PMX_K1_ROLE_SPLIT") && atoi(getenv("PMX_K1_ROLE_SPLIT")) == 0) &&
-            (int64_t)(c->plan.gridX - 1) * c->plan.RP * 128 < c->Mk && !(getenv("PMX_K1_GFIX") && atoi(getenv("PMX_K1_GFIX")) == 0)) {
+        if (rc != PMX_OK) break;
+        facts.chain = g.chainL > 0; facts.prof = g.prof != nullptr; facts.y16 = g.y16 != 0;
+        if (c->k1 == K1_BF16_V7 || facts.inst == K1_V7) {
+            rc = k1_timed(c, [&] { return grad_launch_bf16_v7(g, k1_flags_bf16_v7(facts), c->stream); });
+            break;
+        }
+        // <.., GF>: the correction's three stages on this launch's idle waves instead of three launches behind it (k_gfix_dev.h).  The context's side of
+        // it: a path that can repeat the iteration after a fault, a context that has not fallen back, every region of the plan inside the matrix (an empty
+        // region returns before the stages).  The region test cannot fail with today's planner (plan_row_regions: gridX = ceil(panels / RP), whole column
+        // regions) and no test reaches its other arm; it stands because the kernel's `T <= 0` return comes before the stages, and a planner that left a
+        // region empty would otherwise turn every launch into a 20 ms time-out.  The launch's side -- both gradients wanted on the <HH, RS> instance, no
+        // phase profile, PMX_K1_GFIX not 0 -- is k1_flags_f16_v8's; the ride is armed if and only if the decided instance is <.., GF>, and GfixRide::seq
+        // counts rides, nothing else.
+        facts.ride = !c->k1_sync_check && !c->gfix_ride_off && !c->gfix_ride_hold && c->fixArrive != nullptr && (int64_t)(c->plan.gridX - 1) * c->plan.RP * 128 < c->Mk;
+        const unsigned flags = k1_flags_f16_v8(facts, k1_read_switches());
+        rides = (flags & V8_GF) != 0;
+        if (rides) {
             if (c->fixSeq >= (1u << 30)) {       // (the words are compared for equality: start over long before the number wraps)
                 HIP_CHECK(hipMemsetAsync(c->fixArrive, 0, (size_t)2 * GFIX_RIDE_WGS * sizeof(unsigned), c->stream));
                 c->fixSeq = 0;
@@ -1420,7 +1425,7 @@ static int enqueue_grad_once(pmx_ctx* c, const float* A, const float* St, int do
             g.gfix.seq = ++c->fixSeq;
             g.gfix.inject = c->hook_inject_gfix > 0 && (int)c->fixSeq == c->hook_inject_gfix;
         }
-        if (rc == PMX_OK) rc = k1_timed(c, [&] { return v8 ? grad_launch_f16_v8(g, inst, c->stream, &rode) : grad_launch_bf16_v7(g, c->stream); });
+        rc = k1_timed(c, [&] { return grad_launch_f16_v8(g, flags, c->stream); });
         break;
     }
     case K1_BF16: {
@@ -1430,16 +1435,10 @@ static int enqueue_grad_once(pmx_ctx* c, const float* A, const float* St, int do
         ps.K = (int)c->Kk; ps.KP = c->KP;
         ps.status = c->dstatus;
         launch_presplit(ps, c->stream);
-        GradBfArgs g{};
-        g.Y = c->Y; g.ldY = c->ldY;
+        GradBfArgs g = k1_common_args<GradBfArgs>(c, doA, doS);
         g.Ap = c->Bp[0]; g.At = c->Bt[0]; g.Sp = c->Bp[1]; g.Stt = c->Bt[1];
         g.MPad = c->rowsPad[0]; g.NPad = c->rowsPad[1];
-        g.slabA = c->slab[0]; g.slabS = c->slab[1];
-        g.lossPart = c->lossPart;
-        g.status = c->dstatus;
-        g.M = (int)c->Mk; g.N = (int)c->Nk; g.K = (int)c->Kk;
-        g.RP = c->plan.RP;
-        g.doA = doA; g.doS = doS;
+        g.K = (int)c->Kk;
         g.prof = c->k1prof;
         g.W = c->W; g.ldW = c->ldW;
         rc = k1_timed(c, [&] { return grad_launch_bf16(c->plan, g, c->stream); });
@@ -1451,19 +1450,20 @@ static int enqueue_grad_once(pmx_ctx* c, const float* A, const float* St, int do
             g.fold = fold;
             if (c->chainL > 0) rc = chain_arm(c, g);     // k_grad_f32_pc<.., CHAIN>
         }
+        facts.chain = g.chainL > 0;
         if (rc == PMX_OK)
-            rc = k1_timed(c, [&] { return k1_small(c->k1) ? grad_launch_small(c->plan, g, c->stream) : c->k1 == K1_F32PC ? grad_launch_f32pc(c->plan, g, c->stream) : grad_launch_f32(c->plan, g, c->stream); });
+            rc = k1_timed(c, [&] { return k1_small(c->k1) ? grad_launch_small(c->plan, g, c->stream) : c->k1 == K1_F32PC ? grad_launch_f32pc(c->plan, g, k1_flags_f32_pc(g.K, facts), c->stream) : grad_launch_f32(c->plan, g, c->stream); });
         break;
     }
     }
     if (rc != PMX_OK) return rc;
-    if (grad) c->fix_on = inst == K1_HH;
+    if (grad) c->fix_on = facts.inst == K1_HH;
     // what the high x high residual left out, as one more slab per block (k_gfix.hip).  In the launch stream: the three launches depend on the
     // factors only, but nothing fits BESIDE K1 (its waves hold all 512 registers of every SIMD) -- measured on a stream of their own they sat
     // behind K1's workgroups and the pass got 2 % slower (profiles/r05_a_gfix_side_stream.txt).  K1_F16_V8's two-gradient pass carries them itself, on
-    // waves that idle at both ends of the launch (rode: k_grad_f16_v8<.., GF>); every other route, and a context whose ride has faulted, launches them here.
-    if (rode) { c->gfixRides += 1; return PMX_OK; }
-    if (inst == K1_HH) { c->gfixTriples += 1; return enqueue_gfix(c, A, St, doA, doS, c->stream); }
+    // waves that idle at both ends of the launch (rides: k_grad_f16_v8<.., GF>); every other route, and a context whose ride has faulted, launches them here.
+    if (rides) { c->gfixRides += 1; return PMX_OK; }
+    if (facts.inst == K1_HH) { c->gfixTriples += 1; return enqueue_gfix(c, A, St, doA, doS, c->stream); }
     return PMX_OK;
 }
 
@@ -1474,7 +1474,7 @@ static int enqueue_grad(pmx_ctx* c, const float* A, const float* St, int doA, in
     // behind the launch yet -- refused: the context leaves the fp16 kernels and the same gradient pass runs in exact fp32
     rc = read_status(c);
     if (rc != PMX_OK) return rc;
-    if (c->hstatus->k1_fault != 4) return PMX_OK;
+    if (c->hstatus->k1_fault != K1_FAULT_RANGE) return PMX_OK;
     int again = 0;
     rc = chain_fault_fallback(c, &again);
     if (rc != PMX_OK) return rc;
@@ -1847,8 +1847,8 @@ extern "C" int pmx_grad(pmx_ctx* c) {
         HIP_CHECK(hipStreamSynchronize(c->stream));
         return PMX_OK;
     }
-    // One attempt per repairable fault class and one more: a refused range (k1_fault 4) leaves the fp16 kernels, a chain fault (1-3) the chains, the
-    // correction riding in K1 (5) the ride -- each can happen once per context, and two of them share a cause (workgroups not co-resident).  A pass
+    // One attempt per repairable fault class and one more: a refused range (K1_FAULT_RANGE) leaves the fp16 kernels, a chain fault (K1_FAULT_LATE, _XCD, _INJECTED)
+    // the chains, the correction riding in K1 (K1_FAULT_GFIX) the ride -- each can happen once per context, and two of them share a cause (workgroups not co-resident).  A pass
     // that still faults after that is an error: the fold was skipped under the halt and G holds an older gradient.
     bool clean = false;
     for (int attempt = 0; attempt < 4 && !clean; ++attempt) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/pmx.h"
+#include "k1_instance.h"               // K1's families, instances, fault codes and launch-time switches (no HIP in it)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -71,8 +72,7 @@ struct DevStatus {
     int eig_iters[2];
     int tail_fault;      // k_ada_tail: its census barrier found the workgroups not co-resident; nothing was written (host falls back to the separate kernels)
     int pad2;
-    int k1_fault;        // k_grad_f16_v8<CHAIN>: 1 a chain predecessor never arrived, 2 it runs on another XCD (host falls back to slabs);
-                         // (3: injected by the tests) [r4] 4: a two-term fp16 K1 found the residual's bound too far above max|Y| for ONE fp16 scale (host falls back to exact fp32)
+    int k1_fault;        // K1Fault (k1_instance.h): a K1 launch found its chain hand-off, its fp16 range or its ride not to hold; nothing was updated, the host repairs and repeats
 };
 enum { HALT_NONE = 0, HALT_CONVERGED = 1, HALT_NEED_SUB = 2, HALT_ERROR = 3,
        HALT_RETRY = 4,   // (host view) a kernel reported a recoverable fault before anything was updated: re-enqueue from it_done
@@ -158,34 +158,3 @@ struct Tall {
     } while (0)
 
 void pmx_set_error(const char* fmt, ...);
-
-// ------------------------------------------------------------------------------------------
-// K1's families: pmx_api.hip's select_k1 picks one per context (pmx_k1_info reports it, include/pmx.h)
-// ------------------------------------------------------------------------------------------
-enum K1Kind {
-    K1_SMALL,        // k_grad_small (K <= 16, few million entries), any mode
-    K1_F32,          // k_grad_f32: exact fp32, any shape
-    K1_F32PC,        // k_grad_f32_pc: exact fp32, producer / consumer (K = 32 / 64, M % 128 = 0, N % 256 = 0)
-    K1_BF16,         // k_grad_bf16 / k_grad_bf16_pipe on presplit terms (modes bf16x3 / f16x2, K <= 64)
-    K1_BF16_V7,      // k_grad_bf16_v7: split-bf16 on fp32 operands (K = 64, M % 128 = 0, N % 256 = 0)
-    K1_F16_V8,       // k_grad_f16_v8: two-term fp16 (mode f16x2 at the shapes of K1_BF16_V7)
-    K1_F16_K128,     // k_grad_f16_k128: two-term fp16 at K = 128
-    K1_F16_K32,      // k_grad_f16_k32: two-term fp16 at K = 32 (no weights)
-    K1_F64_SMALL,    // fp64 contexts (k_small_f64.hip, k_big_f64.hip)
-    K1_F64_BIG,
-};
-// the instance a launch of a family runs: PLAIN; R3 (three terms per operand in the residual); HH (the high x high residual, the rest as a
-// correction slab, k_gfix.hip); V7 (k_grad_bf16_v7 in place of k_grad_f16_v8: Y or W cannot be fetched in 8-byte pairs)
-enum K1Inst { K1_PLAIN, K1_R3, K1_HH, K1_V7 };
-// r3: pmx_ctx::f16_r3; grad: a gradient is wanted (the loss-only pass has nowhere to put a correction); pairs: Y and W fetchable in 8-byte pairs
-static inline K1Inst k1_instance(K1Kind k, int r3, bool hasW, bool grad, bool pairs) {
-    switch (k) {
-    case K1_F16_V8:
-        if (!pairs) return K1_V7;
-        if (!r3 || hasW) return K1_PLAIN;                  // (a weighted context keeps two terms)
-        return r3 == 2 && grad ? K1_HH : K1_R3;
-    case K1_F16_K128: return r3 == 2 && !hasW && grad ? K1_HH : K1_PLAIN;
-    case K1_F16_K32: return r3 ? K1_R3 : K1_PLAIN;        // (no weights)
-    default: return K1_PLAIN;
-    }
-}
