@@ -109,10 +109,7 @@ __global__ __launch_bounds__(256) void k_gram_reduce(GramReduceArgs a) {
     const int n = a.KP * a.KP;
     if ((int)blockIdx.x == (n * 8 + 255) / 256) {          // the extra workgroup: the stopping test (block y == 0 only)
         if (blockIdx.y == 0 && a.dec_partials != nullptr) pgm_decide_body(a.dec_status, a.dec_partials, a.dec_e_rel, 1, false);
-        if (blockIdx.y == 0 && a.dec_bsdmm.status != nullptr) {
-            __shared__ double dscratch[EW_WAVES];
-            bsdmm_decide_body(a.dec_bsdmm, dscratch);
-        }
+        if (blockIdx.y == 0 && a.dec_bsdmm.status != nullptr) bsdmm_decide_body(a.dec_bsdmm);
         return;
     }
     const int f = blockIdx.y;

@@ -86,6 +86,19 @@ __device__ __forceinline__ double wave_max(double v) {
     v = fmax(v, __shfl_xor(v, 32));
     return v;
 }
+// max that lets a NaN through, like np.max (fmaxf / fmax drop NaNs): Psi goes NaN with the iterate, and the reference's
+// gamma = Alpha / np.max(Psi) then poisons the whole proximal loop visibly instead of continuing on a partly NaN block
+__device__ __forceinline__ float nanmaxf(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : fmaxf(a, b); }
+__device__ __forceinline__ double nanmax(double a, double b) { return (a != a || b != b) ? __builtin_nan("") : fmax(a, b); }
+__device__ __forceinline__ double wave_nanmax(double v) {
+    v = nanmax(v, dpp_d<DPP_XOR1>(v));
+    v = nanmax(v, dpp_d<DPP_XOR2>(v));
+    v = nanmax(v, dpp_d<DPP_HALF_MIRROR>(v));
+    v = nanmax(v, dpp_d<DPP_MIRROR>(v));
+    v = nanmax(v, swz16_d(v));
+    v = nanmax(v, __shfl_xor(v, 32));
+    return v;
+}
 
 template <int PAT>
 __device__ __forceinline__ double swz_d(double v) {
@@ -125,8 +138,14 @@ __device__ __forceinline__ double wave_sum16(const double (&v)[16]) {
     return z;
 }
 
-// block-wide sum of NV doubles; thread 0 writes dst[i * stride]
-template <int NV>
+// Write-through (`sc1`, agent-scope relaxed) stores and loads of per-workgroup records: what one workgroup publishes for
+// another INSIDE a launch (the last-arrival stopping test of k_pgm_update, the grid barriers of k_ada_tail) without
+// release / acquire fences -- MI355X_MICROARCH.md, "sc0 sc1 stores and loads both sides".
+__device__ __forceinline__ double sc1_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void sc1_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// block-wide sum of NV doubles; thread i writes dst[i * stride] (WT: write-through)
+template <int NV, bool WT = false>
 __device__ __forceinline__ void block_sum_store(double (&v)[NV], double* dst, int64_t stride, double* scratch /* >= NV*EW_WAVES */) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
@@ -139,69 +158,66 @@ __device__ __forceinline__ void block_sum_store(double (&v)[NV], double* dst, in
     if (threadIdx.x < NV) {
         double s = 0.0;
         for (int q = 0; q < EW_WAVES; ++q) s += scratch[threadIdx.x * EW_WAVES + q];
-        dst[threadIdx.x * stride] = s;
+        if constexpr (WT) sc1_store(dst + threadIdx.x * stride, s);
+        else dst[threadIdx.x * stride] = s;
     }
 }
 
-// fold one slot's EW_BLOCKS partials: every WAVE does it on its own (EW_BLOCKS/64 coalesced loads per
-// lane + shuffles, no LDS, no barrier), in a fixed order, so every thread of the grid gets the same value.
-__device__ __forceinline__ double fold_partials(const double* part, double* /*scratch*/) {
+// The operations the per-workgroup partials are folded with: start value, combine, and the tree over a wave's lanes.
+struct FoldSum {
+    static __device__ __forceinline__ double init() { return 0.0; }
+    static __device__ __forceinline__ double comb(double a, double b) { return a + b; }
+    static __device__ __forceinline__ double wave(double v) { return wave_sum(v); }
+};
+struct FoldMax {
+    static __device__ __forceinline__ double init() { return -1.0; }
+    static __device__ __forceinline__ double comb(double a, double b) { return fmax(a, b); }
+    static __device__ __forceinline__ double wave(double v) { return wave_max(v); }
+};
+struct FoldNanMax {
+    static __device__ __forceinline__ double init() { return -1.0; }
+    static __device__ __forceinline__ double comb(double a, double b) { return nanmax(a, b); }
+    static __device__ __forceinline__ double wave(double v) { return wave_nanmax(v); }
+};
+// fold the EW_BLOCKS partials of NS slots: every WAVE does it on its own (EW_BLOCKS/64 coalesced loads per lane and slot +
+// shuffles, no LDS, no barrier), in a fixed order, so every thread of the grid gets the same values.  The loads of all slots
+// are issued before the first combine (one memory latency); each slot is then combined over i ascending and through the
+// operation's wave tree.  wt: write-through loads (partials published inside the same launch).  It is an argument, constant
+// at every call once inlined, and no template parameter: pgm_decide_body passes its own on, and its code inside the
+// gradient kernels that carry the stopping test stays what it was.
+template <class OP = FoldSum, int NS>
+__device__ __forceinline__ void fold_partials(const double* const (&part)[NS], double (&out)[NS], bool wt = false) {
     const int lane = threadIdx.x & 63;
-    double v = 0.0;
+    double u[NS][EW_BLOCKS / 64];
 #pragma unroll
-    for (int i = 0; i < EW_BLOCKS / 64; ++i) v += part[i * 64 + lane];
-    return wave_sum(v);
+    for (int q = 0; q < NS; ++q)
+#pragma unroll
+        for (int i = 0; i < EW_BLOCKS / 64; ++i) u[q][i] = wt ? sc1_load(part[q] + i * 64 + lane) : part[q][i * 64 + lane];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) {
+        double v = OP::init();
+#pragma unroll
+        for (int i = 0; i < EW_BLOCKS / 64; ++i) v = OP::comb(v, u[q][i]);
+        out[q] = OP::wave(v);
+    }
 }
-__device__ __forceinline__ double fold_partials_max(const double* part, double* /*scratch*/) {
+// One slot: the same loads, order and tree.  Written out, not fold_partials<OP, 1>: load-combine-load-combine is the
+// statement order the single-slot folds have always had, and the compiler's output for the fp64 kernels that call this
+// (k64b_ada_sub, k_big_f64.hip) follows the statement order -- through the template their registers come out renumbered.
+template <class OP = FoldSum>
+__device__ __forceinline__ double fold_partials(const double* part, bool wt = false) {
     const int lane = threadIdx.x & 63;
-    double v = -1.0;
+    double v = OP::init();
 #pragma unroll
-    for (int i = 0; i < EW_BLOCKS / 64; ++i) v = fmax(v, part[i * 64 + lane]);
-    return wave_max(v);
+    for (int i = 0; i < EW_BLOCKS / 64; ++i) v = OP::comb(v, wt ? sc1_load(part + i * 64 + lane) : part[i * 64 + lane]);
+    return OP::wave(v);
 }
+// the forms k_big_f64.hip calls (a scratch pointer that nothing reads; the NaN-passing maximum by name)
+__device__ __forceinline__ double fold_partials(const double* part, double*) { return fold_partials(part); }
+__device__ __forceinline__ double fold_partials_nanmax(const double* part) { return fold_partials<FoldNanMax>(part); }
 
 __device__ __forceinline__ double* part_ptr(double* partials, int slot, int blk) {
     return partials + ((int64_t)slot * 2 + blk) * EW_BLOCKS;
-}
-
-// Write-through (`sc1`, agent-scope relaxed) stores and loads of per-workgroup records: what one workgroup publishes for
-// another INSIDE a launch (the last-arrival stopping test of k_pgm_update, the grid barriers of k_ada_tail) without
-// release / acquire fences -- MI355X_MICROARCH.md, "sc0 sc1 stores and loads both sides".
-__device__ __forceinline__ double sc1_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void sc1_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// block_sum_store / colsum_store with write-through stores, fold_partials with write-through loads: same trees
-template <int NV>
-__device__ __forceinline__ void block_sum_store_wt(double (&v)[NV], double* dst, int64_t stride, double* scratch) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = wave_sum(v[i]);
-    __syncthreads();
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < NV; ++i) scratch[i * EW_WAVES + w] = v[i];
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        double s = 0.0;
-        for (int q = 0; q < EW_WAVES; ++q) s += scratch[threadIdx.x * EW_WAVES + q];
-        sc1_store(dst + threadIdx.x * stride, s);
-    }
-}
-__device__ __forceinline__ double fold_partials_wt(const double* part) {
-    const int lane = threadIdx.x & 63;
-    double v = 0.0;
-#pragma unroll
-    for (int i = 0; i < EW_BLOCKS / 64; ++i) v += sc1_load(part + i * 64 + lane);
-    return wave_sum(v);
-}
-__device__ __forceinline__ double nanmax(double a, double b);
-__device__ __forceinline__ double wave_nanmax(double v);
-__device__ __forceinline__ double fold_partials_nanmax_wt(const double* part) {
-    const int lane = threadIdx.x & 63;
-    double v = -1.0;
-#pragma unroll
-    for (int i = 0; i < EW_BLOCKS / 64; ++i) v = nanmax(v, sc1_load(part + i * 64 + lane));
-    return wave_nanmax(v);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -664,7 +680,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_pgm_update(PgmArgs a) {
     // the partial sums go out write-through, the ticket follows them (vmcnt(0): they have landed), and the last arrival
     // reads everybody's partials write-through as well: no fence (a release here would write back the whole L2 -- the
     // factors this kernel has just stored -- once per workgroup: 30 us at 4096 x 4096 x 32 instead of 12)
-    block_sum_store_wt<2>(red, part_ptr(a.partials, SL_DIFF2, j) + blockIdx.x, (int64_t)2 * EW_BLOCKS, scratch);
+    block_sum_store<2, true>(red, part_ptr(a.partials, SL_DIFF2, j) + blockIdx.x, (int64_t)2 * EW_BLOCKS, scratch);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -777,15 +793,14 @@ struct BtCollectArgs {
     int do_block[2];
 };
 __global__ __launch_bounds__(EW_THREADS) void k_bt_collect(BtCollectArgs a) {
-    __shared__ double scratch[EW_WAVES];
     if (chain_halted(a.status)) return;
     for (int j = 0; j < 2; ++j) {
         if (!a.do_block[j]) continue;
-        const double d1 = fold_partials(part_ptr(a.partials, SL_BT0, j), scratch);
-        const double d2 = fold_partials(part_ptr(a.partials, SL_DIFF2, j), scratch);
-        const double n2 = fold_partials(part_ptr(a.partials, SL_NORM2, j), scratch);
-        const double mg = fold_partials_max(part_ptr(a.partials, SL_BT0 + 1, j), scratch);
-        const double mx = fold_partials_max(part_ptr(a.partials, SL_BT0 + 2, j), scratch);
+        const double d1 = fold_partials(part_ptr(a.partials, SL_BT0, j));
+        const double d2 = fold_partials(part_ptr(a.partials, SL_DIFF2, j));
+        const double n2 = fold_partials(part_ptr(a.partials, SL_NORM2, j));
+        const double mg = fold_partials<FoldMax>(part_ptr(a.partials, SL_BT0 + 1, j));
+        const double mx = fold_partials<FoldMax>(part_ptr(a.partials, SL_BT0 + 2, j));
         if (threadIdx.x == 0) {
             a.status->bt[j][0] = d1; a.status->bt[j][1] = d2; a.status->bt[j][2] = mg; a.status->bt[j][3] = mx; a.status->bt[j][4] = n2;
         }
@@ -885,15 +900,14 @@ struct BBStepArgs {
     double init_r;
 };
 __global__ __launch_bounds__(EW_THREADS) void k_bb_step(BBStepArgs a) {
-    __shared__ double scratch[EW_WAVES];
     if (chain_halted(a.status)) return;
     for (int j = 0; j < 2; ++j) {
-        const double ss = fold_partials(part_ptr(a.partials, SL_BB0 + 0, j), scratch);
-        const double sy = fold_partials(part_ptr(a.partials, SL_BB0 + 1, j), scratch);
-        const double yy = fold_partials(part_ptr(a.partials, SL_BB0 + 2, j), scratch);
-        const double gg = fold_partials(part_ptr(a.partials, SL_BB0 + 3, j), scratch);
-        const double mx = fold_partials_max(part_ptr(a.partials, SL_BB0 + 4, j), scratch);
-        const double mg = fold_partials_max(part_ptr(a.partials, SL_BB0 + 5, j), scratch);
+        const double ss = fold_partials(part_ptr(a.partials, SL_BB0 + 0, j));
+        const double sy = fold_partials(part_ptr(a.partials, SL_BB0 + 1, j));
+        const double yy = fold_partials(part_ptr(a.partials, SL_BB0 + 2, j));
+        const double gg = fold_partials(part_ptr(a.partials, SL_BB0 + 3, j));
+        const double mx = fold_partials<FoldMax>(part_ptr(a.partials, SL_BB0 + 4, j));
+        const double mg = fold_partials<FoldMax>(part_ptr(a.partials, SL_BB0 + 5, j));
         if (threadIdx.x == 0) {
             DevStatus* st = a.status;
             double step;
@@ -959,42 +973,34 @@ struct DecideArgs {
     double e_rel[2];
     int check;          // evaluate the convergence test
 };
-__device__ __forceinline__ void pgm_decide_body(DevStatus* st, double* partials, const double (&e_rel)[2], int check, bool wt) {
-    double d[2], n[2];
-    {   // the four sums' partials are requested together (one memory latency), then folded in fold_partials' order
-        const int lane = threadIdx.x & 63;
-        const double* q[4] = {part_ptr(partials, SL_DIFF2, 0), part_ptr(partials, SL_NORM2, 0), part_ptr(partials, SL_DIFF2, 1), part_ptr(partials, SL_NORM2, 1)};
-        double u[4][EW_BLOCKS / 64];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int i = 0; i < EW_BLOCKS / 64; ++i) u[k][i] = wt ? sc1_load(q[k] + i * 64 + lane) : q[k][i * 64 + lane];
-        double r[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            double v = 0.0;
-#pragma unroll
-            for (int i = 0; i < EW_BLOCKS / 64; ++i) v += u[k][i];
-            r[k] = wave_sum(v);
-        }
-        d[0] = r[0]; n[0] = r[1]; d[1] = r[2]; n[1] = r[3];
+// The outer stopping test (algorithms.py:130-135, :403-410) as the one thread that closes an iteration publishes it: per block the
+// verdict d <= e^2 n and the two sums; with `check`, a run whose blocks have both converged stops the chain.  test = 0: no
+// verdict is formed, conv = 0 (adaprox without check_convergence, or with its test left to k_shard_post).  count: the call
+// ends an iteration (it_done advances before a halt can be seen); 0 where the test is a deferred one (k_shard_post*).
+__device__ __forceinline__ void publish_outer_test(DevStatus* st, const double (&d)[2], const double (&n)[2], const double (&e_rel)[2], int check, int test = 1,
+                                                   int count = 0) {
+    int all = 1;
+    for (int j = 0; j < 2; ++j) {
+        const int c = test ? (d[j] <= e_rel[j] * e_rel[j] * n[j]) : 0;
+        st->conv[j] = c;
+        st->norms[j][0] = d[j];
+        st->norms[j][1] = n[j];
+        all &= c;
     }
+    if (count) st->it_done += 1;
+    if (check && all) {
+        st->stopped = 1;
+        chain_halt(st, HALT_CONVERGED);
+    }
+}
+__device__ __forceinline__ void pgm_decide_body(DevStatus* st, double* partials, const double (&e_rel)[2], int check, bool wt) {
+    // the four sums' partials are requested together (one memory latency)
+    const double* const q[4] = {part_ptr(partials, SL_DIFF2, 0), part_ptr(partials, SL_NORM2, 0), part_ptr(partials, SL_DIFF2, 1), part_ptr(partials, SL_NORM2, 1)};
+    double r[4];
+    fold_partials(q, r, wt);
     if (threadIdx.x == 0) {
-        int all = 1;
-        for (int j = 0; j < 2; ++j) {
-            const int c = d[j] <= e_rel[j] * e_rel[j] * n[j];
-            st->conv[j] = c;
-            st->norms[j][0] = d[j];
-            st->norms[j][1] = n[j];
-            all &= c;
-        }
-        st->it_done += 1;
-        if (check && all) {
-            st->stopped = 1;
-            st->reason = HALT_CONVERGED;
-            __threadfence();
-            st->halt = 1;
-        }
+        const double d[2] = {r[0], r[2]}, n[2] = {r[1], r[3]};
+        publish_outer_test(st, d, n, e_rel, check, 1, 1);
     }
 }
 __global__ __launch_bounds__(EW_THREADS) void k_pgm_decide(DecideArgs a) {
@@ -1284,7 +1290,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_pgm_unity(PgmUnityArgs aa) {
         block_sum_store<2>(red, part_ptr(a.partials, SL_DIFF2, j) + blockIdx.x, (int64_t)2 * EW_BLOCKS, scratch);
         return;
     }
-    block_sum_store_wt<2>(red, part_ptr(a.partials, SL_DIFF2, j) + blockIdx.x, (int64_t)2 * EW_BLOCKS, scratch);
+    block_sum_store<2, true>(red, part_ptr(a.partials, SL_DIFF2, j) + blockIdx.x, (int64_t)2 * EW_BLOCKS, scratch);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1379,26 +1385,6 @@ __device__ __forceinline__ float moment_elem(const MomentArgs& a, const MomentSc
     psi_out = psi;
     return (float)((double)xo - upd);
 }
-// max that lets a NaN through, like np.max (fmaxf / fmax drop NaNs): Psi goes NaN with the iterate, and the reference's
-// gamma = Alpha / np.max(Psi) then poisons the whole proximal loop visibly instead of continuing on a partly NaN block
-__device__ __forceinline__ float nanmaxf(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : fmaxf(a, b); }
-__device__ __forceinline__ double nanmax(double a, double b) { return (a != a || b != b) ? __builtin_nan("") : fmax(a, b); }
-__device__ __forceinline__ double wave_nanmax(double v) {
-    v = nanmax(v, dpp_d<DPP_XOR1>(v));
-    v = nanmax(v, dpp_d<DPP_XOR2>(v));
-    v = nanmax(v, dpp_d<DPP_HALF_MIRROR>(v));
-    v = nanmax(v, dpp_d<DPP_MIRROR>(v));
-    v = nanmax(v, swz16_d(v));
-    v = nanmax(v, __shfl_xor(v, 32));
-    return v;
-}
-__device__ __forceinline__ double fold_partials_nanmax(const double* part) {
-    const int lane = threadIdx.x & 63;
-    double v = -1.0;
-#pragma unroll
-    for (int i = 0; i < EW_BLOCKS / 64; ++i) v = nanmax(v, part[i * 64 + lane]);
-    return wave_nanmax(v);
-}
 
 template <int NC>
 __global__ __launch_bounds__(EW_THREADS) void k_ada_moment(MomentArgs a) {
@@ -1470,6 +1456,17 @@ struct SubArgs {
     int has_prox[2];
 };
 
+// How many passes a proximal loop took, judged from the folded sums of passes t0 .. t0 + nt - 1 (sums[2 q] = |z_new - z|^2,
+// sums[2 q + 1] = |z|^2 of pass t0 + q): the first pass that meets the test or reaches prox_max_iter ends it; 0: it goes on.
+__device__ __forceinline__ int sub_tau_scan(const double* sums, int nt, int t0, double e_rel, int prox_max_iter) {
+    int tau = 0;
+    for (int q = 0; q < nt && tau == 0; ++q) {
+        const double d = sums[2 * q], n = sums[2 * q + 1];
+        if ((d <= e_rel * e_rel * n) || (t0 + q + 1 >= prox_max_iter)) tau = t0 + q + 1;
+    }
+    return tau;
+}
+
 // If the loop of block j finished BEFORE pass a.t, returns the number of passes it took (tau >= 1); otherwise 0.
 // Uniform across the workgroup (and across workgroups).  The passes to judge are those of the previous launch,
 // [a.t - a.nt, a.t): wave w folds the sum (pass w >> 1, kind w & 1) in the usual fixed order, then every thread
@@ -1486,15 +1483,11 @@ __device__ __forceinline__ int sub_finished_before(const SubArgs& a, int j, doub
     const int w = threadIdx.x >> 6;
     if (w < 2 * a.nt) {
         const int pass = t0 + (w >> 1);
-        const double v = fold_partials(part_ptr(a.partials, SL_SUBR0 + 2 * (pass % SUB_RING) + (w & 1), j), scratch);
+        const double v = fold_partials(part_ptr(a.partials, SL_SUBR0 + 2 * (pass % SUB_RING) + (w & 1), j));
         if ((threadIdx.x & 63) == 0) scratch[w] = v;
     }
     __syncthreads();
-    int tau = 0;
-    for (int q = 0; q < a.nt && tau == 0; ++q) {
-        const double d = scratch[2 * q], n = scratch[2 * q + 1];
-        if ((d <= a.e_rel[j] * a.e_rel[j] * n) || (t0 + q + 1 >= a.prox_max_iter)) tau = t0 + q + 1;
-    }
+    const int tau = sub_tau_scan(scratch, a.nt, t0, a.e_rel[j], a.prox_max_iter);
     __syncthreads();   // scratch is reused by the caller
     if (tau > 0 && blockIdx.x == 0 && threadIdx.x == 0) {
         a.status->sub_tau[j] = tau;
@@ -1504,18 +1497,43 @@ __device__ __forceinline__ int sub_finished_before(const SubArgs& a, int j, doub
     return tau;
 }
 
-// step size data of the sub-iteration of block j (algorithms.py:384): gamma = Alpha / max(Psi), ratio = gamma / Alpha
+// step sizes of a proximal loop (algorithms.py:384): gamma = Alpha / max(Psi), ratio = gamma / Alpha
 template <int NC>
-__device__ __forceinline__ void sub_steps(const SubArgs& a, int j, double* scratch, float (&gam)[NC], float (&rat)[NC]) {
-    (void)scratch;
-    const double maxpsi = fold_partials_nanmax(part_ptr(a.partials, SL_MAXPSI, j));
-    const int l32_ = threadIdx.x & 31;
+__device__ __forceinline__ void ada_loop_steps(const float (&alpha)[NC], double maxpsi, float (&gam)[NC], float (&rat)[NC]) {
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        const int kk = l32_ + 32 * c;
-        const float al = kk < a.K ? a.status->alpha[j][kk] : 0.f;
-        gam[c] = al / (float)maxpsi;
-        rat[c] = gam[c] / al;                     // NaN if alpha == 0, as in the reference
+        gam[c] = alpha[c] / (float)maxpsi;
+        rat[c] = gam[c] / alpha[c];               // NaN if alpha == 0, as in the reference
+    }
+}
+// the same for block j of the chain of kernels, from the folded maxima of k_ada_moment and the control block's alpha
+template <int NC>
+__device__ __forceinline__ void sub_steps(const SubArgs& a, int j, float (&gam)[NC], float (&rat)[NC]) {
+    const double maxpsi = fold_partials<FoldNanMax>(part_ptr(a.partials, SL_MAXPSI, j));
+    const int l32_ = threadIdx.x & 31;
+    float alpha[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) alpha[c] = l32_ + 32 * c < a.K ? a.status->alpha[j][l32_ + 32 * c] : 0.f;
+    ada_loop_steps<NC>(alpha, maxpsi, gam, rat);
+}
+
+// One pass of a proximal loop on a row (algorithms.py:385-399): v = prox(z - ratio Psi (z - x), gamma), then z = v.  SUMS: the
+// two sums of the pass's stopping test, |v - z|^2 and |z|^2 (z: before the pass), are added to d2 and n2.
+template <int NC, bool ME, bool SUMS>
+__device__ __forceinline__ void ada_pass(float (&z)[NC], const float (&x)[NC], const float (&ps)[NC], const bool (&ok)[NC], const ProxSeq& prox,
+                                         const float (&gam)[NC], const float (&rat)[NC], float& d2, float& n2) {
+    float v[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) v[c] = z[c] - rat[c] * ps[c] * (z[c] - x[c]);
+    prox_row<float, NC, 32, ME>(v, ok, prox, gam);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        if (SUMS && ok[c]) {
+            const float d = v[c] - z[c];
+            d2 += d * d;
+            n2 += z[c] * z[c];
+        }
+        z[c] = v[c];
     }
 }
 
@@ -1536,7 +1554,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_ada_sub(SubArgs a) {
     const float* zc = b == 0 ? a.X[j] : a.zb[j][(b - 1) & 1];
     float* zn = a.zb[j][b & 1];
     float gam[NC], rat[NC];
-    sub_steps<NC>(a, j, scratch, gam, rat);
+    sub_steps<NC>(a, j, gam, rat);
     float d2[NT], n2[NT];
 #pragma unroll
     for (int q = 0; q < NT; ++q) { d2[q] = 0.f; n2[q] = 0.f; }
@@ -1552,21 +1570,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_ada_sub(SubArgs a) {
             ps[c] = ok[c] ? a.Psi[j][e] : 0.f;
         }
 #pragma unroll
-        for (int q = 0; q < NT; ++q) {
-            float v[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) v[c] = z[c] - rat[c] * ps[c] * (z[c] - x[c]);
-            prox_row<float, NC, 32, ME>(v, ok, a.prox[j], gam);
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                if (ok[c]) {
-                    const float d = v[c] - z[c];
-                    d2[q] += d * d;
-                    n2[q] += z[c] * z[c];
-                }
-                z[c] = v[c];
-            }
-        }
+        for (int q = 0; q < NT; ++q) ada_pass<NC, ME, true>(z, x, ps, ok, a.prox[j], gam, rat, d2[q], n2[q]);
 #pragma unroll
         for (int c = 0; c < NC; ++c)
             if (ok[c]) zn[r * K + l32 + 32 * c] = z[c];
@@ -1590,6 +1594,25 @@ struct FinishArgs {
     float* absmax_out;   // [2][EW_BLOCKS] per-workgroup max |X_j| of the iterate written here (the fp16 K1's operand
                          // scales, saving its own k_absmax pass), or nullptr
 };
+// One row of the finish phase: X <- x, and what the end of the iteration needs of it -- max |x|, the outer test's two sums against
+// the iterate before the update (Xp; `check` only) and the column sums.  e0: index of the lane's first component of the row.
+template <int NC>
+__device__ __forceinline__ void ada_finish_row(const float (&x)[NC], const bool (&ok)[NC], float* X, const float* Xp, int64_t e0, bool check,
+                                               float& xmax, float& d2, float& n2, float (&cs)[NC]) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        if (!ok[c]) continue;
+        const int64_t e = e0 + 32 * c;
+        X[e] = x[c];
+        xmax = fmaxf(xmax, fabsf(x[c]));
+        if (check) {
+            const float d = x[c] - Xp[e];
+            d2 += d * d;
+            n2 += x[c] * x[c];
+        }
+        cs[c] += x[c];
+    }
+}
 template <int NC, bool ME = false>
 __global__ __launch_bounds__(EW_THREADS) void k_ada_finish(FinishArgs a) {
     __shared__ double scratch[2 * EW_WAVES];
@@ -1626,7 +1649,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_ada_finish(FinishArgs a) {
         } else {
             src = b == 0 ? a.s.X[j] : a.s.zb[j][(b - 1) & 1];    // its input, q + 1 passes to redo
             replay = q + 1;
-            sub_steps<NC>(a.s, j, scratch, gam, rat);
+            sub_steps<NC>(a.s, j, gam, rat);
         }
     }
     float* X = a.s.X[j];
@@ -1650,30 +1673,10 @@ __global__ __launch_bounds__(EW_THREADS) void k_ada_finish(FinishArgs a) {
                 x[c] = ok[c] ? X[e] : 0.f;
                 ps[c] = ok[c] ? a.s.Psi[j][e] : 0.f;
             }
-            for (int q = 0; q < replay; ++q) {
-                float v[NC];
-#pragma unroll
-                for (int c = 0; c < NC; ++c) v[c] = z[c] - rat[c] * ps[c] * (z[c] - x[c]);
-                prox_row<float, NC, 32, ME>(v, ok, a.s.prox[j], gam);
-#pragma unroll
-                for (int c = 0; c < NC; ++c) z[c] = v[c];
-            }
+            float no_d2 = 0.f, no_n2 = 0.f;
+            for (int q = 0; q < replay; ++q) ada_pass<NC, ME, false>(z, x, ps, ok, a.s.prox[j], gam, rat, no_d2, no_n2);
         }
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            if (ok[c]) {
-                const int64_t e = r * K + l32 + 32 * c;
-                const float x = z[c];
-                X[e] = x;
-                xmax = fmaxf(xmax, fabsf(x));
-                if (a.check_convergence) {
-                    const float d = x - a.Xp[j][e];
-                    d2 += d * d;
-                    n2 += x * x;
-                }
-                cs[c] += x;
-            }
-        }
+        ada_finish_row<NC>(z, ok, X, a.Xp[j], r * K + l32, a.check_convergence, xmax, d2, n2, cs);
     ROW_LOOP_END
     double red[2] = {(double)d2, (double)n2};
     block_sum_store<2>(red, part_ptr(a.s.partials, SL_DIFF2, j) + blockIdx.x, (int64_t)2 * EW_BLOCKS, scratch);
@@ -1700,48 +1703,37 @@ struct AdaDecideArgs {
     int has_prox[2];
     int host_tau[2];     // passes of a proximal loop that ran around a user-defined prox on the host (block j), else 0
 };
+// End of an adaprox iteration (one thread): the passes its proximal loops took, the iteration counter, the outer test
+__device__ __forceinline__ void ada_close_iteration(DevStatus* st, const int (&tau)[2], const double (&d)[2], const double (&n)[2], const double (&e_rel)[2], int check) {
+    for (int j = 0; j < 2; ++j) {
+        st->sub_total[j] += tau[j];
+        st->last_tau[j] = tau[j];
+    }
+    publish_outer_test(st, d, n, e_rel, check, check, 1);
+}
 __global__ __launch_bounds__(EW_THREADS) void k_ada_decide(AdaDecideArgs a) {
-    __shared__ double scratch[EW_WAVES];
     DevStatus* st = a.al.status;
     if (chain_halted(st)) return;
     __shared__ int need;
     if (threadIdx.x == 0) need = st->need_sub[0] | st->need_sub[1];
     __syncthreads();
     if (need) {   // the enqueued proximal sub-iterations did not suffice: stop the chain, the host resumes
-        if (threadIdx.x == 0) {
-            st->reason = HALT_NEED_SUB;
-            __threadfence();
-            st->halt = 1;
-        }
+        if (threadIdx.x == 0) chain_halt(st, HALT_NEED_SUB);
         return;
     }
     double d[2] = {0, 0}, n[2] = {0, 0};
     if (a.check_convergence)
         for (int j = 0; j < 2; ++j) {
-            d[j] = fold_partials(part_ptr(a.partials, SL_DIFF2, j), scratch);
-            n[j] = fold_partials(part_ptr(a.partials, SL_NORM2, j), scratch);
+            d[j] = fold_partials(part_ptr(a.partials, SL_DIFF2, j));
+            n[j] = fold_partials(part_ptr(a.partials, SL_NORM2, j));
         }
     compute_alpha(a.al);   // step sizes for the NEXT iteration from the updated factors (nmf.py:93)
     if (threadIdx.x == 0) {
-        int all = 1;
+        const int tau[2] = {a.has_prox[0] ? st->sub_tau[0] : a.host_tau[0], a.has_prox[1] ? st->sub_tau[1] : a.host_tau[1]};
+        ada_close_iteration(st, tau, d, n, a.e_rel, a.check_convergence);
         for (int j = 0; j < 2; ++j) {
-            const int c = a.check_convergence ? (d[j] <= a.e_rel[j] * a.e_rel[j] * n[j]) : 0;
-            st->conv[j] = c;
-            st->norms[j][0] = d[j];
-            st->norms[j][1] = n[j];
-            all &= c;
-            const int tau = a.has_prox[j] ? st->sub_tau[j] : a.host_tau[j];
-            st->sub_total[j] += tau;
-            st->last_tau[j] = tau;
             st->sub_done[j] = 0;
             st->sub_tau[j] = 0;
-        }
-        st->it_done += 1;
-        if (a.check_convergence && all) {
-            st->stopped = 1;
-            st->reason = HALT_CONVERGED;
-            __threadfence();
-            st->halt = 1;
         }
     }
 }
@@ -1826,9 +1818,7 @@ __device__ __forceinline__ void gb_sync(GridBar* b, unsigned e, DevStatus* st) {
             __builtin_amdgcn_s_sleep(4);
             if ((spins & 1023u) == 0 && wall_clock64() - t0 > 10000000) {
                 st->tail_fault = 2;
-                st->reason = HALT_ERROR;
-                __threadfence();
-                st->halt = 1;
+                chain_halt(st, HALT_ERROR);
                 break;
             }
         }
@@ -1906,9 +1896,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_ada_tail(TailArgs a) {
         if (s_word & 1u) {
             if (blockIdx.x == 0 && tid == 0) {
                 st->tail_fault = 1;
-                st->reason = HALT_ERROR;
-                __threadfence();
-                st->halt = 1;
+                chain_halt(st, HALT_ERROR);
             }
             return;
         }
@@ -1969,29 +1957,15 @@ __global__ __launch_bounds__(EW_THREADS) void k_ada_tail(TailArgs a) {
         stamp();
         bool done0 = !a.m.has_prox[0], done1 = !a.m.has_prox[1];
         // max Psi per block (algorithms.py:384), kept in two scalars; gamma and gamma / alpha are re-derived where needed
-        double mp0, mp1;
+        double mp[2];
         {   // both blocks' partials requested before the first of them is reduced: one memory latency, not two
-            const int lane = tid & 63;
-            const double* q0 = part_ptr(a.m.partials, SL_MAXPSI, 0);
-            const double* q1 = part_ptr(a.m.partials, SL_MAXPSI, 1);
-            double u0[EW_BLOCKS / 64], u1[EW_BLOCKS / 64];
-#pragma unroll
-            for (int i = 0; i < EW_BLOCKS / 64; ++i) { u0[i] = sc1_load(q0 + i * 64 + lane); u1[i] = sc1_load(q1 + i * 64 + lane); }
-            double v0 = -1.0, v1 = -1.0;
-#pragma unroll
-            for (int i = 0; i < EW_BLOCKS / 64; ++i) { v0 = nanmax(v0, u0[i]); v1 = nanmax(v1, u1[i]); }
-            mp0 = wave_nanmax(v0);
-            mp1 = wave_nanmax(v1);
+            const double* const q[2] = {part_ptr(a.m.partials, SL_MAXPSI, 0), part_ptr(a.m.partials, SL_MAXPSI, 1)};
+            fold_partials<FoldNanMax>(q, mp, true);
         }
         stamp();
         auto steps = [&](int j, float (&gam)[NC], float (&rat)[NC]) {
-            const float mp = (float)(j ? mp1 : mp0);
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const float al = j ? alpha1[c] : alpha0[c];
-                gam[c] = al / mp;
-                rat[c] = gam[c] / al;                    // NaN if alpha == 0, as in the reference
-            }
+            if (j) ada_loop_steps<NC>(alpha1, mp[1], gam, rat);
+            else ada_loop_steps<NC>(alpha0, mp[0], gam, rat);
         };
         // up to TAIL_NT passes (n of them) from the round's starting iterate; SUMS: also the two sums of the stopping test
         auto passes = [&](int j, int i, int n, bool first_round, const float (&gam)[NC], const float (&rat)[NC], float (&z)[NC],
@@ -2006,23 +1980,8 @@ __global__ __launch_bounds__(EW_THREADS) void k_ada_tail(TailArgs a) {
                 if (!ok[c]) { x[c] = 0.f; ps[c] = 0.f; z[c] = 0.f; }
             }
 #pragma unroll
-            for (int q = 0; q < TAIL_NT; ++q) {
-                if (q < n) {
-                    float v[NC];
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) v[c] = z[c] - rat[c] * ps[c] * (z[c] - x[c]);
-                    prox_row(v, ok, a.prox[j], gam);
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) {
-                        if (SUMS && ok[c]) {
-                            const float d = v[c] - z[c];
-                            d2[q] += d * d;
-                            n2[q] += z[c] * z[c];
-                        }
-                        z[c] = v[c];
-                    }
-                }
-            }
+            for (int q = 0; q < TAIL_NT; ++q)
+                if (q < n) ada_pass<NC, false, SUMS>(z, x, ps, ok, a.prox[j], gam, rat, d2[q], n2[q]);
         };
         using yes = std::integral_constant<bool, true>;
         using no = std::integral_constant<bool, false>;
@@ -2098,15 +2057,11 @@ __global__ __launch_bounds__(EW_THREADS) void k_ada_tail(TailArgs a) {
                 const int w = tid >> 6;
                 __syncthreads();
                 if (w < 2 * nt) {
-                    const double v = fold_partials_wt(part_ptr(a.m.partials, SL_SUBR0 + 2 * TAIL_NT * (round & 3) + w, j));
+                    const double v = fold_partials(part_ptr(a.m.partials, SL_SUBR0 + 2 * TAIL_NT * (round & 3) + w, j), true);
                     if ((tid & 63) == 0) scratch[w] = v;
                 }
                 __syncthreads();
-                int tau = 0;
-                for (int q = 0; q < nt && tau == 0; ++q) {
-                    const double d = scratch[2 * q], n = scratch[2 * q + 1];
-                    if ((d <= a.e_rel[j] * a.e_rel[j] * n) || (t0 + q + 1 >= a.prox_max_iter)) tau = t0 + q + 1;
-                }
+                const int tau = sub_tau_scan(scratch, nt, t0, a.e_rel[j], a.prox_max_iter);
                 __syncthreads();
                 const int keep = tau > 0 ? tau - t0 : nt;            // passes of this round that count
                 if (!(round == 0 && keep == nt)) {                   // (round 0 already left its end state in Lz)
@@ -2146,20 +2101,10 @@ __global__ __launch_bounds__(EW_THREADS) void k_ada_tail(TailArgs a) {
         for (int i = 0; i < a.slots[j]; ++i) {
             const int64_t r = hw + (int64_t)i * nhw;
             if (r >= rows) break;
+            float x[NC];
 #pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                if (!ok[c]) continue;
-                const int64_t e = r * K + l32 + 32 * c;
-                const float x = src[slot(j, i, c)];
-                a.m.X[j][e] = x;
-                xmax = fmaxf(xmax, fabsf(x));
-                if (a.m.check_convergence) {
-                    const float d = x - a.m.Xp[j][e];
-                    d2 += d * d;
-                    n2 += x * x;
-                }
-                cs[c] += x;
-            }
+            for (int c = 0; c < NC; ++c) x[c] = ok[c] ? src[slot(j, i, c)] : 0.f;
+            ada_finish_row<NC>(x, ok, a.m.X[j], a.m.Xp[j], r * K + l32, a.m.check_convergence, xmax, d2, n2, cs);
         }
         f_d2[j] = d2; f_n2[j] = n2; f_xmax[j] = xmax;
 #pragma unroll
@@ -2241,30 +2186,14 @@ __global__ __launch_bounds__(EW_THREADS) void k_ada_tail(TailArgs a) {
         double d[2] = {0, 0}, n[2] = {0, 0};
         if (a.m.check_convergence)
             for (int j = 0; j < 2; ++j) {
-                d[j] = fold_partials_wt(part_ptr(a.m.partials, SL_DIFF2, j));
-                n[j] = fold_partials_wt(part_ptr(a.m.partials, SL_NORM2, j));
+                d[j] = fold_partials(part_ptr(a.m.partials, SL_DIFF2, j), true);
+                n[j] = fold_partials(part_ptr(a.m.partials, SL_NORM2, j), true);
             }
         if (tid == 0) {
-            int all = 1;
-            for (int j = 0; j < 2; ++j) {
-                const int c = (a.m.check_convergence && a.decide_check) ? (d[j] <= a.e_rel[j] * a.e_rel[j] * n[j]) : 0;
-                st->conv[j] = c;
-                st->norms[j][0] = d[j];
-                st->norms[j][1] = n[j];
-                all &= c;
-                const int tau = a.m.has_prox[j] ? (j ? tau1 : tau0) : 0;
-                st->sub_total[j] += tau;
-                st->last_tau[j] = tau;
-            }
-            st->it_done += 1;
             bar->epoch[0] = ep;
             if (a.prof != nullptr) a.prof[nstamp++] = wall_clock64();
-            if (a.m.check_convergence && a.decide_check && all) {
-                st->stopped = 1;
-                st->reason = HALT_CONVERGED;
-                __threadfence();
-                st->halt = 1;
-            }
+            const int tau[2] = {a.m.has_prox[0] ? tau0 : 0, a.m.has_prox[1] ? tau1 : 0};
+            ada_close_iteration(st, tau, d, n, a.e_rel, a.m.check_convergence && a.decide_check);
         }
     }
 }
@@ -2516,7 +2445,7 @@ struct BsdmmDecideArgs {
     const float* comm_scalars;   // row-sharded block A: all-reduced sums [d2, x2, q0..] instead of the local partials
 };
 // (body: also the extra workgroup of k_gram_reduce, 256 threads -- fold_partials is per wave, any workgroup size)
-__device__ __forceinline__ void bsdmm_decide_body(const BsdmmDecideArgs& a, double* scratch) {
+__device__ __forceinline__ void bsdmm_decide_body(const BsdmmDecideArgs& a) {
     const int j = a.j;
     double d2, x2, q[4 * PMX_MAX_G];
     if (a.comm_scalars != nullptr) {
@@ -2524,9 +2453,9 @@ __device__ __forceinline__ void bsdmm_decide_body(const BsdmmDecideArgs& a, doub
         x2 = (double)a.comm_scalars[1];
         for (int i = 0; i < 4 * a.n_g; ++i) q[i] = (double)a.comm_scalars[2 + i];
     } else {
-        d2 = fold_partials(part_ptr(a.partials, SL_DIFF2, j), scratch);
-        x2 = fold_partials(part_ptr(a.partials, SL_NORM2, j), scratch);
-        for (int i = 0; i < 4 * a.n_g; ++i) q[i] = fold_partials(part_ptr(a.partials, SL_G0 + i, j), scratch);
+        d2 = fold_partials(part_ptr(a.partials, SL_DIFF2, j));
+        x2 = fold_partials(part_ptr(a.partials, SL_NORM2, j));
+        for (int i = 0; i < 4 * a.n_g; ++i) q[i] = fold_partials(part_ptr(a.partials, SL_G0 + i, j));
     }
     if (threadIdx.x == 0) {
         DevStatus* st = a.status;
@@ -2552,17 +2481,14 @@ __device__ __forceinline__ void bsdmm_decide_body(const BsdmmDecideArgs& a, doub
             st->it_done += 1;
             if (st->conv[0] && st->conv[1]) {
                 st->stopped = 1;
-                st->reason = HALT_CONVERGED;
-                __threadfence();
-                st->halt = 1;
+                chain_halt(st, HALT_CONVERGED);
             }
         }
     }
 }
 __global__ __launch_bounds__(EW_THREADS) void k_bsdmm_decide(BsdmmDecideArgs a) {
-    __shared__ double scratch[EW_WAVES];
     if (chain_halted(a.status)) return;
-    bsdmm_decide_body(a, scratch);
+    bsdmm_decide_body(a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2591,26 +2517,8 @@ constexpr int SHARD_HALT_SLOT = 31;
 // round trips (column-sum fold, stopping sums, Gram copy) that workgroup 0 used to run BEHIND its share of the rows -- the whole
 // launch waited on that one workgroup (25 us for 25 MB of traffic); now they run beside the fold, one piece per workgroup.
 constexpr int PACK_XWG = 3;
-// four (or fewer) partial-sum folds with every load in flight before the first add; each sum in fold_partials' own order
-template <int NS>
-__device__ __forceinline__ void fold_partials_many(const double* const (&part)[NS], double (&out)[NS]) {
-    const int lane = threadIdx.x & 63;
-    double v[NS][EW_BLOCKS / 64];
-#pragma unroll
-    for (int q = 0; q < NS; ++q)
-#pragma unroll
-        for (int i = 0; i < EW_BLOCKS / 64; ++i) v[q][i] = part[q][i * 64 + lane];
-#pragma unroll
-    for (int q = 0; q < NS; ++q) {
-        double t = 0.0;
-#pragma unroll
-        for (int i = 0; i < EW_BLOCKS / 64; ++i) t += v[q][i];
-        out[q] = wave_sum(t);
-    }
-}
 template <int NC>
 __global__ __launch_bounds__(EW_THREADS) void k_shard_pack(PackArgs a) {
-    __shared__ double scratch[EW_WAVES];
     if (chain_halted(a.status)) {
         if (blockIdx.x == 0 && threadIdx.x == 0) a.comm[a.N * a.K + a.KP * a.KP + MAXK + SHARD_HALT_SLOT] = 1.f;
         return;
@@ -2654,10 +2562,10 @@ __global__ __launch_bounds__(EW_THREADS) void k_shard_pack(PackArgs a) {
     } else {                             // stopping sums of block 0 (+ bsdmm's extra slots); [31] = the halt flag: 0 here
         const double* const two[2] = {a.partials + ((int64_t)SL_DIFF2 * 2 + 0) * EW_BLOCKS, a.partials + ((int64_t)SL_NORM2 * 2 + 0) * EW_BLOCKS};
         double dn[2];
-        fold_partials_many<2>(two, dn);
+        fold_partials(two, dn);
         if (t < 32) sc[t] = t == 0 ? (float)dn[0] : (t == 1 ? (float)dn[1] : 0.f);
         for (int i = 0; i < a.n_extra; ++i) {
-            const double q = fold_partials(a.partials + ((int64_t)(SL_G0 + i) * 2 + 0) * EW_BLOCKS, scratch);
+            const double q = fold_partials(a.partials + ((int64_t)(SL_G0 + i) * 2 + 0) * EW_BLOCKS);
             if (t == 0) sc[2 + i] = (float)q;
         }
     }
@@ -2675,11 +2583,7 @@ struct GramInArgs {
 __global__ __launch_bounds__(256) void k_shard_gram_in(GramInArgs a) {
     if (chain_halted(a.status)) return;
     if (a.peer_halt != nullptr && *a.peer_halt > 0.5f) {     // another rank is halted: stop here, before this iteration's update
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            a.wstatus->reason = HALT_PEER;
-            __threadfence();
-            a.wstatus->halt = 1;
-        }
+        if (blockIdx.x == 0 && threadIdx.x == 0) chain_halt(a.wstatus, HALT_PEER);
         return;
     }
     const int e = blockIdx.x * 256 + threadIdx.x;
@@ -2697,35 +2601,19 @@ struct ShardPostArgs {
     int do_alpha;            // adaprox only
 };
 __global__ __launch_bounds__(EW_THREADS) void k_shard_post(ShardPostArgs a) {
-    __shared__ double scratch[EW_WAVES];
     DevStatus* st = a.al.status;
     if (chain_halted(st)) return;
     if (a.scalars[SHARD_HALT_SLOT] > 0.5f) {         // another rank is halted: stop before this iteration's update
-        if (threadIdx.x == 0) {
-            st->reason = HALT_PEER;
-            __threadfence();
-            st->halt = 1;
-        }
+        if (threadIdx.x == 0) chain_halt(st, HALT_PEER);
         return;
     }
     if (a.do_alpha) compute_alpha(a.al);
     if (a.check_convergence && a.have_prev) {
-        const double dS = fold_partials(part_ptr(a.partials, SL_DIFF2, 1), scratch);
-        const double nS = fold_partials(part_ptr(a.partials, SL_NORM2, 1), scratch);
+        const double dS = fold_partials(part_ptr(a.partials, SL_DIFF2, 1));
+        const double nS = fold_partials(part_ptr(a.partials, SL_NORM2, 1));
         if (threadIdx.x == 0) {
-            const double dA = (double)a.scalars[0], nA = (double)a.scalars[1];
-            const int cA = dA <= a.e_rel[0] * a.e_rel[0] * nA;
-            const int cS = dS <= a.e_rel[1] * a.e_rel[1] * nS;
-            st->conv[0] = cA;
-            st->conv[1] = cS;
-            st->norms[0][0] = dA; st->norms[0][1] = nA;
-            st->norms[1][0] = dS; st->norms[1][1] = nS;
-            if (cA && cS) {
-                st->stopped = 1;
-                st->reason = HALT_CONVERGED;
-                __threadfence();
-                st->halt = 1;
-            }
+            const double d[2] = {(double)a.scalars[0], dS}, n[2] = {(double)a.scalars[1], nS};
+            publish_outer_test(st, d, n, a.e_rel, 1);
         }
     }
 }
@@ -2794,7 +2682,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_shard_pack_split(PackSplitArgs a
     const double* const four[4] = {a.partials + ((int64_t)SL_DIFF2 * 2 + 0) * EW_BLOCKS, a.partials + ((int64_t)SL_NORM2 * 2 + 0) * EW_BLOCKS,
                                    a.partials + ((int64_t)SL_DIFF2 * 2 + 1) * EW_BLOCKS, a.partials + ((int64_t)SL_NORM2 * 2 + 1) * EW_BLOCKS};
     double sums[4];
-    fold_partials_many<4>(four, sums);
+    fold_partials(four, sums);
     for (int q = 0; q < a.world; ++q) {
         float* ex = a.comm + q * a.chunk + ex0;
         if (a.gramA != nullptr)
@@ -2821,11 +2709,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_shard_post_split(ShardPostSplitA
     if (chain_halted(st)) return;
     const float* sc = a.extras + 2 * MAXK;
     if (sc[SHARD_HALT_SLOT] > 0.5f) {              // another rank is halted: stop before this iteration's update
-        if (threadIdx.x == 0) {
-            st->reason = HALT_PEER;
-            __threadfence();
-            st->halt = 1;
-        }
+        if (threadIdx.x == 0) chain_halt(st, HALT_PEER);
         return;
     }
     const int t = threadIdx.x;
@@ -2833,19 +2717,8 @@ __global__ __launch_bounds__(EW_THREADS) void k_shard_post_split(ShardPostSplitA
         for (int j = 0; j < 2; ++j)
             st->alpha[j][t] = a.use_fixed ? a.fixed[j] : (float)((double)a.extras[j * MAXK + t] / (double)a.rows_global[j]) / 10.f;
     if (a.check_convergence && a.have_prev && t == 0) {
-        const double dA = (double)sc[0], nA = (double)sc[1], dS = (double)sc[2], nS = (double)sc[3];
-        const int cA = dA <= a.e_rel[0] * a.e_rel[0] * nA;
-        const int cS = dS <= a.e_rel[1] * a.e_rel[1] * nS;
-        st->conv[0] = cA;
-        st->conv[1] = cS;
-        st->norms[0][0] = dA; st->norms[0][1] = nA;
-        st->norms[1][0] = dS; st->norms[1][1] = nS;
-        if (cA && cS) {
-            st->stopped = 1;
-            st->reason = HALT_CONVERGED;
-            __threadfence();
-            st->halt = 1;
-        }
+        const double d[2] = {(double)sc[0], (double)sc[2]}, n[2] = {(double)sc[1], (double)sc[3]};
+        publish_outer_test(st, d, n, a.e_rel, 1);
     }
 }
 

@@ -87,6 +87,12 @@ struct ProxSeq {           // device copy of pmx_proxseq
 __device__ __forceinline__ bool chain_halted(const DevStatus* st) {
     return __builtin_nontemporal_load(&st->halt) != 0;
 }
+// stop the chain (one thread): the reason is visible before the flag that makes every later kernel a no-op
+__device__ __forceinline__ void chain_halt(DevStatus* st, int reason) {
+    st->reason = reason;
+    __threadfence();
+    st->halt = 1;
+}
 
 // ------------------------------------------------------------------------------------------
 // [r6] The step rule's Gram fold (k_gram_reduce's work) riding in the first workgroups of the NEXT K1 launch.

@@ -125,6 +125,9 @@ def _ada_cases():
         out += [a(s, scheme="adamx", b1="sched")]          # cold: iteration 0 reads b1[-1], Vhat stays None
         out += [a(s, scheme="nadam", check=False), a(s, scheme="amsgrad", warm=True, check=False, **nat)]
         out += [a(s, scheme="adam", prox="ap_unity", hits_pmi=True)]                          # the loop runs into prox_max_iter = 3
+        # loops longer than one launch / round of 4 passes: S ends inside the second one (k_ada_finish replays from a later launch's
+        # input, the tail redoes the passes that count); at 18 the 16-pass sum ring wraps and the chain asks the host for more passes
+        out += [a(s, scheme="adam", prox="ap_unity", hits_pmi=True, pmi=pmi) for pmi in (6, 18)]
         out += [a(s, scheme="adam", step="rule"), a(s, scheme="amsgrad", warm=True, step="rule")]   # nmf.step_adaprox on the device
         out += [a(s, scheme="adam", table="shrink", b1=0.0, eps=1e-3, stop_at=5, **dict(nat, e_rel=3e-3))]    # the outer test fires at a known iteration
     for s in SUBSET:
