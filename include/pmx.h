@@ -26,7 +26,8 @@ extern "C" {
 #endif
 
 #define PMX_ABI_VERSION 7 /* v7 grew, additively, by one op code (PMX_PROX_COMPONENTS) and three symbols (pmx_prox_table,
-                             pmx_prox_array_tables, pmx_gfix_info): no struct changed its layout, so the number stayed */
+                             pmx_prox_array_tables, pmx_gfix_info), then by three more (pmx_prox_view, pmx_prox_flat,
+                             pmx_pointer_device): no struct changed its layout, so the number stayed */
 
 /* ---- status codes -------------------------------------------------------------------- */
 enum {
@@ -106,7 +107,7 @@ enum {
 /* One proximal operator.  `unit` says which sum prox_unity* normalises by, in DEVICE layout:
  * 0 = along the K components of one row (numpy axis=1 for A, axis=0 for S),
  * 1 = along the rows, per component     (numpy axis=0 for A, axis=1 for S): a sum over the whole factor per application.
- *     Taken by the stand-alone operator entry points (pmx_prox_apply / pmx_prox_array) and by pmx_pgm_begin -- pgm / FISTA
+ *     Taken by the stand-alone operator entry points (pmx_prox_apply / pmx_prox_array / pmx_prox_view) and by pmx_pgm_begin -- pgm / FISTA
  *     with any of its step rules, no line search, no host_prox, not in fp64 or row-sharded contexts: the update then runs as
  *     a chain of 1 + (applications per iteration) launches.  Every other solver entry point answers PMX_E_UNSUPPORTED.
  * `relative` = 1 is the reference's type="relative" (threshold multiplied by the step the
@@ -293,8 +294,8 @@ int pmx_step_adaprox(pmx_ctx* ctx, float* out);
  * step_k: K per-component steps (scalar steps: K copies). block selects rows (M or N).        */
 int pmx_prox_apply(pmx_ctx* ctx, int buf, const pmx_proxseq* prox, const float* step_k);
 /* context-free variant: `prox(X, step)` on a HOST array X (rows x K float32, K <= 128, updated in
- * place): copies to the device, runs the operator kernel, copies back.  This is what calling
- * proxmin.operators.prox_* directly on an ndarray maps to. */
+ * place): copies to the device, runs the operator kernel, copies back.  float32 and host memory only: calling
+ * proxmin.operators.prox_* on an array maps to pmx_prox_view / pmx_prox_flat below, which keep the array's type and place. */
 int pmx_prox_array(int device, float* X, int64_t rows, int K, const pmx_proxseq* prox, const float* step_k);
 /* [ABI v7] Table `index` (0 .. PMX_MAX_TABLES - 1) of the context: K rows of the 24-byte pmx_prox, row k = the operator of
  * component k (op, thresh, relative; unit = reserved = 0).  A row is an element-wise operator: id, zero, plus, min, max, hard,
@@ -312,6 +313,37 @@ int pmx_prox_table(pmx_ctx* ctx, int index, const pmx_prox* rows, int K);
  * prox_components, directly on an ndarray maps to. */
 int pmx_prox_array_tables(int device, float* X, int64_t rows, int K, const pmx_proxseq* prox, const float* step_k,
                           const pmx_prox* tables, int ntables);
+/* [ABI v7, additive] `prox(X, step)` in the array's OWN element type and, for an array in HBM, on its own memory: what calling
+ * proxmin.operators.prox_* on a float32 or float64 array maps to (the reference mutates at the array's dtype: operators.py:33-38,
+ * :138-160; pmx_prox_array above is float32 and host-only and stays as it is).
+ *   X          rows x K elements of float (is_f64 = 0) or double (1), K <= 128, element (r, k) at X + r * stride0 + k * stride1 (in
+ *              elements).  on_device = 0: host memory, dense and row-major (strides (K, 1)): uploaded to GPU `host_device`, updated,
+ *              downloaded.  on_device = 1: device memory, updated IN PLACE, nothing copied: a row-major view (stride1 == 1, stride0 >= K:
+ *              any pitch, e.g. the first columns of a wider tensor) or a column-major one (stride0 == 1, stride1 >= rows: a K x N `S`
+ *              seen as N rows of K components, through 32 x 32 LDS tiles) -- pmx_factor_from_device's rule; the stride of an axis of
+ *              extent 1 does not count.  Only the view's rows x K elements are written.  The GPU is the one the pointer lives on
+ *              (hipPointerGetAttributes; host_device is ignored), everything enqueued on that GPU before the call is finished first
+ *              (a hipDeviceSynchronize: an array interface carries no stream) and the work is complete on return.
+ *              The calling thread's current device is put back before the call returns (host_device or the pointer's GPU is
+ *              current only inside it).
+ *   prox       the sequence, including prox_unity* along the rows (unit = 1: two launches per application; per-thread sums in row
+ *              order in the array's type, folded in double in a fixed order) and PMX_PROX_COMPONENTS with `tables` as in
+ *              pmx_prox_array_tables (ntables x K rows, NULL / 0 for none).
+ *   step_k     K per-component steps (scalar steps: K copies) as double: float arrays use (float)step_k[k] and (float)thresh, double
+ *              arrays the doubles themselves.
+ * PMX_E_INVALID, before anything is launched: a NULL argument, K > 128, strides that are neither layout (or a host array that is not
+ * dense), a pointer not aligned to its element size, a table row that is not element-wise, on_device = 1 with a pointer the runtime
+ * does not know as device memory. */
+int pmx_prox_view(void* X, int on_device, int is_f64, int64_t rows, int K, int64_t stride0, int64_t stride1, const pmx_proxseq* prox,
+                  const double* step_k, const pmx_prox* tables, int ntables, int host_device);
+/* [ABI v7, additive] The flat form: a sequence of ELEMENT-WISE operators with one scalar step on `n` contiguous elements (an array of
+ * any shape that is C- or F-contiguous), the tail guarded -- no padding, no copy for device memory.  prox_unity* and
+ * PMX_PROX_COMPONENTS are refused (PMX_E_INVALID): they need the component structure of pmx_prox_view.  Memory, type, device and
+ * ordering as there. */
+int pmx_prox_flat(void* X, int on_device, int is_f64, int64_t n, const pmx_proxseq* prox, double step, int host_device);
+/* [ABI v7, additive] The GPU a device pointer lives on (hipPointerGetAttributes): what the two calls above go by.  PMX_E_INVALID for
+ * anything the runtime does not know as device memory. */
+int pmx_pointer_device(const void* dptr, int* device);
 /* [ABI v4] context-free reductions of utils.BarzilaiBorweinStepper.step called as a FUNCTION on host arrays (utils.py:216-241; inside
  * pgm the rule runs fused, k_bb_reduce / k_bb_step): one block's X, G and the previous call's X_prev, G_prev (both NULL in the first
  * call: s = y = 0), `count` elements of float (is_f64 = 0) or double (1).  out = { sum s^2, sum s y, sum y^2, sum G^2, max|X|, max|G| }

@@ -97,6 +97,10 @@ _SIGNATURES = {
     "pmx_prox_array": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.POINTER(ProxSeq), C.c_void_p]),
     "pmx_prox_table": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Prox), C.c_int]),
     "pmx_prox_array_tables": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.POINTER(ProxSeq), C.c_void_p, C.POINTER(Prox), C.c_int]),
+    "pmx_prox_view": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.POINTER(ProxSeq), C.POINTER(C.c_double),
+                                C.POINTER(Prox), C.c_int, C.c_int]),
+    "pmx_prox_flat": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.POINTER(ProxSeq), C.c_double, C.c_int]),
+    "pmx_pointer_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "pmx_bb_sums": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double)]),
     "pmx_pgm_begin": (C.c_int, [C.c_void_p, C.POINTER(PgmParams)]),
     "pmx_pgm_run": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Result)]),

@@ -36,6 +36,7 @@
 #include "k_grad_f64.hip"
 #include "k_big_f64.hip"
 #include "k_xfer.hip"
+#include "k_prox_view.hip"
 
 // ------------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -2177,6 +2178,181 @@ extern "C" int pmx_bb_sums(int device, int is_f64, const void* X, const void* Xp
         if (e == hipSuccess) e = hipMemcpy(out, part + BBS_BLOCKS * 6, 6 * sizeof(double), hipMemcpyDeviceToHost);
     }
     if (e != hipSuccess) FAIL(PMX_E_HIP, "bb_sums: %s", hipGetErrorString(e));
+    return PMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// operators called on arrays, in the array's type and on the array's own memory (k_prox_view.hip)
+// ------------------------------------------------------------------------------------------------
+// scratch of pmx_prox_view / pmx_prox_flat, one per device, kept between calls like pmx_bb_sums's: the column-sum partials, the
+// per-component tables (device layout: MAXK rows each) and, for host arrays only, the dense copy of the array
+struct PvScratch { char* d = nullptr; size_t bytes = 0; };
+static std::mutex g_pv_mu;
+static PvScratch g_pv_scratch[16];
+constexpr size_t PV_COLPART_BYTES = (size_t)EW_BLOCKS * MAXK * sizeof(double);
+constexpr size_t PV_TABLE_BYTES = (size_t)PMX_MAX_TABLES * MAXK * sizeof(pmx_prox);
+static int pv_scratch(int device, size_t data_bytes, char** out) {      // (g_pv_mu held)
+    const size_t need = PV_COLPART_BYTES + PV_TABLE_BYTES + data_bytes;
+    PvScratch& sc = g_pv_scratch[device];
+    if (sc.bytes < need) {
+        if (sc.d) (void)hipFree(sc.d);
+        sc.d = nullptr;
+        sc.bytes = 0;
+        HIP_CHECK(hipMalloc((void**)&sc.d, need));
+        sc.bytes = need;
+    }
+    *out = sc.d;
+    return PMX_OK;
+}
+// the calling thread's current device, put back when the entry point returns: an operator call on a tensor of another GPU must not
+// move where the caller's next allocation lands
+struct DeviceRestore {
+    int dev = -1;
+    DeviceRestore() { if (hipGetDevice(&dev) != hipSuccess) { dev = -1; (void)hipGetLastError(); } }
+    ~DeviceRestore() { if (dev >= 0) (void)hipSetDevice(dev); }
+};
+// the GPU a pointer lives on; PMX_E_INVALID for anything the runtime does not know as device memory
+static int pointer_device(const void* p, int* device) {
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof(at));
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device < 0 || at.device >= 16) {
+        (void)hipGetLastError();
+        FAIL(PMX_E_INVALID, "%p is not device memory (hipPointerGetAttributes: %s)", p, e != hipSuccess ? hipGetErrorString(e) : "another kind of memory");
+    }
+    *device = at.device;
+    return PMX_OK;
+}
+extern "C" int pmx_pointer_device(const void* dptr, int* device) {
+    if (!dptr || !device) FAIL(PMX_E_INVALID, "NULL argument");
+    return pointer_device(dptr, device);
+}
+
+// one operator sequence on a view: apply_prox_standalone's cut at prox_unity* along the rows, each of them two launches
+template <class T>
+static void apply_prox_view(T* X, int64_t rows, int K, int64_t s0, int64_t s1, const pmx_proxseq& prox, const double* step_k, double* colpart,
+                            const pmx_prox* tab, hipStream_t stream) {
+    ProxViewArgs<T> a{};
+    a.X = X; a.rows = rows; a.K = K; a.s0 = s0; a.s1 = s1;
+    a.colpart = colpart;
+    for (int k = 0; k < K; ++k) a.stepk[k] = (T)step_k[k];
+    if (!prox_long_axis(prox)) {
+        a.prox = to_dev(prox, tab);
+        launch_prox_view<T>(a, stream);
+        return;
+    }
+    const int repeat = prox.repeat < 1 ? 1 : prox.repeat;
+    for (int r = 0; r < repeat; ++r)
+        for (int i = 0; i < prox.n; ++i) {
+            pmx_proxseq one{};
+            one.n = 1; one.repeat = 1; one.seq[0] = prox.seq[i];
+            const bool rows_unity = (one.seq[0].op == PMX_PROX_UNITY || one.seq[0].op == PMX_PROX_UNITY_PLUS) && one.seq[0].unit != 0;
+            a.div = 0; a.sum = 0;
+            if (!rows_unity) {
+                a.prox = to_dev(one, tab);
+                launch_prox_view<T>(a, stream);
+                continue;
+            }
+            if (one.seq[0].op == PMX_PROX_UNITY_PLUS) { one.seq[0].op = PMX_PROX_PLUS; one.seq[0].unit = 0; }   // plus first (operators.py:48-52)
+            else one.n = 0;
+            a.prox = to_dev(one, tab);
+            a.sum = 1;
+            launch_prox_view<T>(a, stream);
+            one.n = 0;
+            a.prox = to_dev(one, tab);
+            a.sum = 0; a.div = 1;
+            launch_prox_view<T>(a, stream);
+        }
+}
+
+extern "C" int pmx_prox_view(void* X, int on_device, int is_f64, int64_t rows, int K, int64_t stride0, int64_t stride1, const pmx_proxseq* prox,
+                             const double* step_k, const pmx_prox* tables, int ntables, int host_device) {
+    if (!X || !prox || !step_k) FAIL(PMX_E_INVALID, "NULL argument");
+    if (rows <= 0 || K <= 0 || K > MAXK) FAIL(PMX_E_INVALID, "prox_view: bad shape rows=%lld K=%d (K <= %d)", (long long)rows, K, MAXK);
+    const size_t es = is_f64 ? sizeof(double) : sizeof(float);
+    if (reinterpret_cast<uintptr_t>(X) % es) FAIL(PMX_E_INVALID, "prox_view: %p is not aligned to its %zu-byte elements", X, es);
+    const bool rowmajor = (stride1 == 1 || K == 1) && (stride0 >= K || rows == 1), colmajor = (stride0 == 1 || rows == 1) && (stride1 >= rows || K == 1);
+    if (!rowmajor && !colmajor)
+        FAIL(PMX_E_INVALID, "prox_view: strides (%lld, %lld) of a %lld x %d view: one of them must be 1 and the other at least the extent it steps over",
+             (long long)stride0, (long long)stride1, (long long)rows, K);
+    if (!on_device && !(stride1 == 1 && stride0 == K)) FAIL(PMX_E_INVALID, "prox_view: a host array is dense and row-major (strides (K, 1))");
+    if (ntables < 0 || ntables > PMX_MAX_TABLES || (ntables > 0 && !tables)) FAIL(PMX_E_INVALID, "prox_view: bad table count %d", ntables);
+    int rc = check_prox(*prox, "prox_view", true, nullptr, ntables);
+    if (rc != PMX_OK) return rc;
+    for (int64_t i = 0; i < (int64_t)ntables * K; ++i)
+        if (!row_op_ok(tables[i].op)) FAIL(PMX_E_INVALID, "prox_view: table row %lld holds op %d, which is not an element-wise operator", (long long)i, tables[i].op);
+    // (an axis of extent 1 is never stepped along: its stride does not count)
+    const int64_t s0 = rowmajor ? (rows > 1 ? stride0 : K) : 1, s1 = rowmajor ? 1 : (K > 1 ? stride1 : rows);
+    int device = host_device;
+    if (on_device) {
+        rc = pointer_device(X, &device);
+        if (rc != PMX_OK) return rc;
+    }
+    if (device < 0 || device >= 16) FAIL(PMX_E_INVALID, "bad device %d", device);
+    DeviceRestore restore;
+    HIP_CHECK(hipSetDevice(device));
+    // The array interface that hands a device pointer over carries no stream: everything enqueued on ANY stream of this device
+    // before the call is finished first (pmx_factor_from_device's rule); the work is complete when the call returns.
+    if (on_device) HIP_CHECK(hipDeviceSynchronize());
+    std::lock_guard<std::mutex> lock(g_pv_mu);           // (also serialises the null-stream work of concurrent callers on the one scratch)
+    const size_t bytes = on_device ? 0 : (size_t)rows * K * es;
+    char* d;
+    rc = pv_scratch(device, bytes, &d);
+    if (rc != PMX_OK) return rc;
+    double* colpart = reinterpret_cast<double*>(d);
+    pmx_prox* dtab = ntables > 0 ? reinterpret_cast<pmx_prox*>(d + PV_COLPART_BYTES) : nullptr;
+    void* arr = on_device ? X : (void*)(d + PV_COLPART_BYTES + PV_TABLE_BYTES);
+    hipError_t e = hipSuccess;
+    for (int t = 0; t < ntables && e == hipSuccess; ++t)
+        e = hipMemcpy(dtab + (size_t)t * MAXK, tables + (size_t)t * K, sizeof(pmx_prox) * K, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !on_device) e = hipMemcpy(arr, X, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        if (is_f64) apply_prox_view<double>((double*)arr, rows, K, s0, s1, *prox, step_k, colpart, dtab, nullptr);
+        else apply_prox_view<float>((float*)arr, rows, K, s0, s1, *prox, step_k, colpart, dtab, nullptr);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = on_device ? hipStreamSynchronize(nullptr) : hipMemcpy(X, arr, bytes, hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) FAIL(PMX_E_HIP, "prox_view: %s", hipGetErrorString(e));
+    return PMX_OK;
+}
+
+extern "C" int pmx_prox_flat(void* X, int on_device, int is_f64, int64_t n, const pmx_proxseq* prox, double step, int host_device) {
+    if (!X || !prox) FAIL(PMX_E_INVALID, "NULL argument");
+    if (n <= 0) FAIL(PMX_E_INVALID, "prox_flat: bad count %lld", (long long)n);
+    const size_t es = is_f64 ? sizeof(double) : sizeof(float);
+    if (reinterpret_cast<uintptr_t>(X) % es) FAIL(PMX_E_INVALID, "prox_flat: %p is not aligned to its %zu-byte elements", X, es);
+    int rc = check_prox(*prox, "prox_flat", true, nullptr, 0);
+    if (rc != PMX_OK) return rc;
+    for (int i = 0; i < prox->n; ++i)
+        if (!row_op_ok(prox->seq[i].op)) FAIL(PMX_E_INVALID, "prox_flat: op %d is not an element-wise operator", prox->seq[i].op);
+    int device = host_device;
+    if (on_device) {
+        rc = pointer_device(X, &device);
+        if (rc != PMX_OK) return rc;
+    }
+    if (device < 0 || device >= 16) FAIL(PMX_E_INVALID, "bad device %d", device);
+    DeviceRestore restore;
+    HIP_CHECK(hipSetDevice(device));
+    if (on_device) HIP_CHECK(hipDeviceSynchronize());
+    std::lock_guard<std::mutex> lock(g_pv_mu);
+    const size_t bytes = on_device ? 0 : (size_t)n * es;
+    char* d;
+    rc = pv_scratch(device, bytes, &d);
+    if (rc != PMX_OK) return rc;
+    void* arr = on_device ? X : (void*)(d + PV_COLPART_BYTES + PV_TABLE_BYTES);
+    hipError_t e = on_device ? hipSuccess : hipMemcpy(arr, X, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        if (is_f64) {
+            ProxFlatArgs<double> a{(double*)arr, n, to_dev(*prox, nullptr), step};
+            launch_prox_flat<double>(a, nullptr);
+        } else {
+            ProxFlatArgs<float> a{(float*)arr, n, to_dev(*prox, nullptr), (float)step};
+            launch_prox_flat<float>(a, nullptr);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = on_device ? hipStreamSynchronize(nullptr) : hipMemcpy(X, arr, bytes, hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) FAIL(PMX_E_HIP, "prox_flat: %s", hipGetErrorString(e));
     return PMX_OK;
 }
 

@@ -108,8 +108,10 @@ class DeviceArrayRef:
         self.ptr, self.shape, self.ld, self.owner = int(cai["data"][0]), shape, ld, obj
         self.dtype = np.dtype(np.float64 if es == 8 else np.float32)
         self.ndim = 2
-        dev = getattr(obj, "device", None)
-        self.device = int(getattr(dev, "index", None) or 0) if dev is not None and not isinstance(dev, int) else int(dev or 0)
+        # the GPU: from the pointer where the runtime knows it, else .device.index (torch) / .device.id (CuPy) / an integer .device;
+        # an object that says nothing about its device is taken to be on GPU 0
+        dev = pointer_device(self.ptr)
+        self.device = dev if dev is not None else (_device_index(obj) if getattr(obj, "device", None) is not None else 0)
 
     def __array__(self, *a, **k):
         raise TypeError("this array lives on the GPU; proxmin_amd adopts it in place")
@@ -135,51 +137,138 @@ class DeviceFactorRef:
     dtype the solvers compute their return values in, `owner` the caller's object."""
 
     def __init__(self, obj):
-        cai = obj.__cuda_array_interface__
-        ts = cai.get("typestr")
-        if ts not in ("<f4", "=f4", "|f4", "<f8", "=f8", "|f8"):
-            raise TypeError("a device-resident factor must be float32 or float64 (got %r)" % (ts,))
-        es = 8 if ts.endswith("8") else 4
-        shape = tuple(int(v) for v in cai["shape"])
-        if len(shape) != 2:
-            raise TypeError("a device-resident factor must be two-dimensional (got shape %r)" % (shape,))
-        data = cai["data"]
-        if bool(data[1]):
-            raise TypeError("a device-resident factor is updated in place: a read-only array cannot be one")
-        strides = cai.get("strides")
-        if strides is None:
-            st = (shape[1], 1)
-        else:
-            if len(strides) != 2 or any(int(s) % es for s in strides):
-                raise TypeError("a device-resident factor's strides %r are not whole elements" % (tuple(strides),))
-            st = tuple(int(s) // es for s in strides)
-        # one unit stride, the other axis stepping over at least that axis's extent (an axis of extent 1 is never stepped along)
-        rowmajor = (st[1] == 1 or shape[1] == 1) and (st[0] >= shape[1] or shape[0] == 1)
-        colmajor = (st[0] == 1 or shape[0] == 1) and (st[1] >= shape[0] or shape[1] == 1)
-        if not (rowmajor or colmajor):
-            if 1 not in st:
-                raise TypeError("a device-resident factor needs unit stride along one of its axes (element strides %r)" % (st,))
-            raise TypeError("a device-resident factor's rows overlap (shape %r, element strides %r)" % (shape, st))
-        if rowmajor:
-            st = (st[0] if shape[0] > 1 else max(shape[1], 1), 1)
-        else:
-            st = (1, st[1] if shape[1] > 1 else max(shape[0], 1))
-        self.ptr, self.shape, self.strides, self.owner = int(data[0]), shape, st, obj
-        self.dtype = np.dtype(np.float64 if es == 8 else np.float32)
+        self.ptr, self.shape, self.strides, self.dtype = _parse_view(obj.__cuda_array_interface__, "a device-resident factor")
+        self.owner = obj
         self.ndim = 2
-        self.device = _device_index(obj)
+        self.device = _device_index(obj, self.ptr)
 
     def __array__(self, *a, **k):
         raise TypeError("this array lives on the GPU; proxmin_amd updates it in place")
 
 
-def _device_index(obj):
-    """the HIP device an array lives on: obj.device.index (torch), obj.device.id (CuPy) or an int"""
+def _parse_header(cai, what):
+    """-> (pointer, shape, element size, element strides or None for a C-contiguous array) of a WRITABLE float32 / float64 array
+    interface; TypeError naming the cause otherwise"""
+    ts = cai.get("typestr")
+    if ts not in ("<f4", "=f4", "|f4", "<f8", "=f8", "|f8"):
+        raise TypeError("%s must be float32 or float64 (got %r)" % (what, ts))
+    es = 8 if ts.endswith("8") else 4
+    shape = tuple(int(v) for v in cai["shape"])
+    data = cai["data"]
+    if bool(data[1]):
+        raise TypeError("%s is updated in place: a read-only array cannot be one" % what)
+    strides = cai.get("strides")
+    if strides is not None:
+        if len(strides) != len(shape) or any(int(s) % es for s in strides):
+            raise TypeError("%s's strides %r are not whole elements" % (what, tuple(strides)))
+        strides = tuple(int(s) // es for s in strides)
+    return int(data[0]), shape, es, strides
+
+
+def _parse_view(cai, what):
+    """-> (pointer, shape, element strides, dtype) of a two-dimensional row- or column-major view with any pitch (the rule of
+    include/pmx.h: pmx_factor_from_device); TypeError naming the cause for anything else"""
+    shape = tuple(int(v) for v in cai["shape"])
+    if len(shape) != 2:
+        ts = cai.get("typestr")
+        if ts not in ("<f4", "=f4", "|f4", "<f8", "=f8", "|f8"):
+            raise TypeError("%s must be float32 or float64 (got %r)" % (what, ts))
+        raise TypeError("%s must be two-dimensional (got shape %r)" % (what, shape))
+    ptr, shape, es, st = _parse_header(cai, what)
+    if st is None:
+        st = (shape[1], 1)
+    # one unit stride, the other axis stepping over at least that axis's extent (an axis of extent 1 is never stepped along)
+    rowmajor = (st[1] == 1 or shape[1] == 1) and (st[0] >= shape[1] or shape[0] == 1)
+    colmajor = (st[0] == 1 or shape[0] == 1) and (st[1] >= shape[0] or shape[1] == 1)
+    if not (rowmajor or colmajor):
+        if 1 not in st:
+            raise TypeError("%s needs unit stride along one of its axes (element strides %r)" % (what, st))
+        raise TypeError("%s's rows overlap (shape %r, element strides %r)" % (what, shape, st))
+    if rowmajor:
+        st = (st[0] if shape[0] > 1 else max(shape[1], 1), 1)
+    else:
+        st = (1, st[1] if shape[1] > 1 else max(shape[0], 1))
+    return ptr, shape, st, np.dtype(np.float64 if es == 8 else np.float32)
+
+
+def pointer_device(ptr):
+    """the GPU a device pointer lives on, as the runtime knows it (pmx_pointer_device: hipPointerGetAttributes); None where it cannot
+    say -- the library is not built, no GPU, or an address it does not know as device memory"""
+    if not os.path.exists(_lib.LIB_PATH):       # not built: nobody to ask (a stale or mismatched library raises in load(), loudly)
+        return None
+    lib = _lib.load()
+    if lib.pmx_device_count() < 1:
+        return None
+    dev = C.c_int(-1)
+    return int(dev.value) if lib.pmx_pointer_device(C.c_void_p(int(ptr)), C.byref(dev)) == 0 else None
+
+
+def _device_index(obj, ptr=None):
+    """the HIP device an array lives on: the pointer's own (a CuPy array carries .device.id, other producers nothing torch-like: the
+    runtime knows), else obj.device.index (torch), obj.device.id (CuPy) or an int"""
+    if ptr is not None:
+        dev = pointer_device(ptr)
+        if dev is not None:
+            return dev
     dev = getattr(obj, "device", None)
     for v in (getattr(dev, "index", None), getattr(dev, "id", None), dev):
         if isinstance(v, (int, np.integer)) and not isinstance(v, bool):
             return int(v)
     raise TypeError("cannot tell which GPU this device-resident factor lives on (no .device.index, .device.id or integer .device)")
+
+
+class DeviceOperandRef:
+    """The argument of an operator of proxmin_amd.operators that lives in HBM and is updated there: anything that speaks
+    `__cuda_array_interface__`, writable, float32 or float64.  Two-dimensional: a row- or column-major view with any pitch
+    (`strides` in elements, DeviceFactorRef's rule).  `flat`: the array is one contiguous run of `size` elements (1-D with unit
+    stride, C- or F-contiguous n-D), which is all an element-wise operator with a scalar step needs; arrays of other dimensions
+    than two must be that.  The GPU is not asked here: the library takes it from the pointer."""
+
+    def __init__(self, obj):
+        what = "a device-resident operator argument"
+        cai = obj.__cuda_array_interface__
+        shape = tuple(int(v) for v in cai["shape"])
+        if len(shape) == 2:
+            self.ptr, self.shape, self.strides, self.dtype = _parse_view(cai, what)
+            # one contiguous run?  Judged on the interface's own strides: _parse_view's normalisation replaces the stride of an axis of
+            # extent 1, and a single column (M, 1) of a wider tensor is a run only if its rows are 1 element apart
+            raw = cai.get("strides")
+            raw = (shape[1], 1) if raw is None else tuple(int(v) // self.dtype.itemsize for v in raw)
+            self.flat = _contiguous(shape, raw)
+        else:
+            self.ptr, self.shape, es, st = _parse_header(cai, what)
+            self.dtype = np.dtype(np.float64 if es == 8 else np.float32)
+            self.strides = None
+            if st is not None and not _contiguous(self.shape, st):
+                raise NotImplementedError("%s of %d dimensions must be C- or F-contiguous (shape %r, element strides %r): only "
+                                          "two-dimensional arrays are taken as row- or column-major views" % (what, len(shape), shape, st))
+            self.flat = True
+        self.size = int(np.prod(self.shape, dtype=np.int64)) if self.shape else 1
+        self.ndim = len(self.shape)
+        self.owner = obj
+
+
+def _contiguous(shape, st):
+    """do these element strides lay `shape` out as one run, in C or in Fortran order?  (axes of extent 1 do not count)"""
+    for order in (range(len(shape) - 1, -1, -1), range(len(shape))):
+        want, good = 1, True
+        for ax in order:
+            if shape[ax] != 1 and st[ax] != want:
+                good = False
+                break
+            want *= shape[ax]
+        if good:
+            return True
+    return False
+
+
+def as_device_operand(obj):
+    """DeviceOperandRef for an operator argument that lives on the GPU, None for host data"""
+    if isinstance(obj, np.ndarray) or not hasattr(obj, "__cuda_array_interface__"):
+        return None
+    if getattr(obj, "is_cuda", True) is False:       # a torch tensor on the host
+        return None
+    return DeviceOperandRef(obj)
 
 
 def as_device_factor(obj):

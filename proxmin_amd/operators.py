@@ -7,8 +7,14 @@ Two uses:
     they are recognised by identity -- the same test as AlternatingProjections.find,
     operators.py:213-224 -- and run FUSED inside the solver kernels; the Python bodies below are
     never called on that path;
-  * called directly on an ndarray they run the same device kernel on that array
-    (`pmx_prox_array`): there is no NumPy implementation in this package.
+  * called directly on an array they run the same operator code on that array, in the array's own element type like the
+    reference (operators.py:33-38, :138-160): float64 arrays in fp64, float32 arrays in fp32 (every other dtype is computed in
+    float32).  A host array goes to the GPU `PMX_DEVICE` names (default 0) and comes back (`pmx_prox_view` / `pmx_prox_flat`);
+    an array that lives in HBM -- anything with `__cuda_array_interface__`, float32 or float64: a torch tensor on the GPU, a
+    CuPy array -- is updated in place on its own GPU, nothing copied, and the object passed in is returned.  Element-wise
+    operators with a scalar step take 1-D and C- or F-contiguous n-D arrays; wherever components, axes or per-component
+    steps matter the array is a 2-D row- or column-major view with any pitch (e.g. `T[3:, :33]`, `St.T`).  `step`, `thresh`
+    and `gamma` are host scalars or host arrays.  There is no NumPy implementation in this package.
 
 Per-component parameters: `thresh` (`gamma`) of the threshold operators may be an array with one value per component, and
 `prox_components` gives every component an operator of its own.  Both become one device entry PMX_PROX_COMPONENTS whose
@@ -18,10 +24,11 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
+import os
 
 import numpy as np
 
-from . import _lib
+from . import _lib, engine
 
 __all__ = ["prox_id", "prox_zero", "prox_plus", "prox_unity", "prox_unity_plus", "prox_min", "prox_max",
            "prox_hard", "prox_hard_plus", "prox_soft", "prox_soft_plus", "prox_max_entropy", "prox_components",
@@ -29,7 +36,7 @@ __all__ = ["prox_id", "prox_zero", "prox_plus", "prox_unity", "prox_unity_plus",
 
 
 # ---------------------------------------------------------------------------------------------
-# direct application on host arrays
+# direct application on arrays (host, or in HBM)
 # ---------------------------------------------------------------------------------------------
 # operators that work entry by entry: what a row of a per-component table may be (include/pmx.h: pmx_prox_table)
 ELEMENTWISE = ("id", "zero", "plus", "min", "max", "hard", "hard_plus", "soft", "soft_plus", "max_entropy")
@@ -75,22 +82,102 @@ def check_tables(seqs, K):
                 raise ValueError("per-component operator parameters: %d values for a factorisation with K = %d components" % (len(tab), K))
 
 
-def _run_rows(rows2d, ps, step_k):
+def _work_dtype(dtype):
+    """the element type an array of this dtype is computed in: its own for float32 and float64, float32 for every other"""
+    return np.dtype(dtype) if np.dtype(dtype) in (np.dtype(np.float32), np.dtype(np.float64)) else np.dtype(np.float32)
+
+
+def _host_device():
+    """the GPU host arrays are sent to: PMX_DEVICE from the environment, else 0 (utils.BarzilaiBorweinStepper's rule); an array that
+    lives on a GPU is worked on where it is"""
+    return int(os.environ.get("PMX_DEVICE", "0"))
+
+
+def _call_view(ptr, on_device, dtype, rows, K, s0, s1, ps, step_k):
+    """pmx_prox_view: `ps` on rows x K elements of `dtype` (float32 / float64), element (r, k) at ptr + r * s0 + k * s1 elements"""
     lib = _lib.require_gpu()
-    buf = np.ascontiguousarray(rows2d, dtype=np.float32)
-    sk = np.ascontiguousarray(np.broadcast_to(np.asarray(step_k, dtype=np.float32).reshape(-1), (buf.shape[1],)))
+    sk = np.ascontiguousarray(np.broadcast_to(np.asarray(step_k, dtype=np.float64).reshape(-1), (K,)))
     tables = seq_tables(ps)
-    if tables:                           # per-component rows: pmx_prox_array_tables takes them next to the sequence
-        check_tables([ps], buf.shape[1])
-        flat = (_lib.Prox * (len(tables) * buf.shape[1]))()
+    flat = None
+    if tables:                           # per-component rows travel next to the sequence: ntables x K of them
+        check_tables([ps], K)
+        flat = (_lib.Prox * (len(tables) * K))()
         for t, tab in enumerate(tables):
-            C.memmove(C.byref(flat, t * buf.shape[1] * C.sizeof(_lib.Prox)), tab, C.sizeof(tab))
-        _lib.check(lib.pmx_prox_array_tables(0, buf.ctypes.data_as(C.c_void_p), buf.shape[0], buf.shape[1], C.byref(ps),
-                                             sk.ctypes.data_as(C.c_void_p), flat, len(tables)))
+            C.memmove(C.byref(flat, t * K * C.sizeof(_lib.Prox)), tab, C.sizeof(tab))
+    _lib.check(lib.pmx_prox_view(C.c_void_p(ptr), int(on_device), int(np.dtype(dtype) == np.float64), rows, K, s0, s1, C.byref(ps),
+                                 sk.ctypes.data_as(C.POINTER(C.c_double)), flat, len(tables), _host_device()))
+
+
+def _call_flat(ptr, on_device, dtype, n, ps, step):
+    """pmx_prox_flat: element-wise `ps` with one step on n contiguous elements"""
+    lib = _lib.require_gpu()
+    _lib.check(lib.pmx_prox_flat(C.c_void_p(ptr), int(on_device), int(np.dtype(dtype) == np.float64), n, C.byref(ps), float(step), _host_device()))
+
+
+def _run_rows(rows2d, ps, step_k):
+    """The one place HOST data meets the device.  `ps` on a two-dimensional host array seen as rows of components (step_k: one
+    step, or one per component), or -- a one-dimensional array -- on its elements with the one step `step_k` (the flat form:
+    element-wise operators only).  -> the result in the dtype it was computed in: the argument itself, updated in place, where it
+    is a dense row-major float32 / float64 array, else a new array."""
+    buf = np.ascontiguousarray(rows2d, dtype=_work_dtype(rows2d.dtype))
+    if buf.ndim == 1:
+        if buf.size:
+            _call_flat(buf.ctypes.data, False, buf.dtype, buf.size, ps, step_k)
         return buf
-    _lib.check(lib.pmx_prox_array(0, buf.ctypes.data_as(C.c_void_p), buf.shape[0], buf.shape[1], C.byref(ps),
-                                  sk.ctypes.data_as(C.c_void_p)))
+    _call_view(buf.ctypes.data, False, buf.dtype, buf.shape[0], buf.shape[1], buf.shape[1], 1, ps, step_k)
     return buf
+
+
+class _Operand:
+    """What an operator was called on.  A host array (anything np.asarray takes) is computed in its own dtype when that is float32
+    or float64 -- in place where its layout allows, else through a contiguous copy -- and in float32 otherwise.  An array in HBM
+    (engine.DeviceOperandRef: `__cuda_array_interface__`, float32 / float64) is updated where it lives; nothing is copied.
+    `X` is what the operator returns: the caller's own object (the ndarray made of it for host data that was not one)."""
+
+    def __init__(self, X):
+        self.ref = engine.as_device_operand(X)
+        if self.ref is not None:
+            self.X, self.shape, self.dtype = X, self.ref.shape, self.ref.dtype
+        else:
+            self.X = X if isinstance(X, np.ndarray) else np.asarray(X)
+            if not self.X.flags.writeable:       # (dense arrays are updated through their address: NumPy's own check would be bypassed)
+                raise ValueError("assignment destination is read-only")
+            self.shape, self.dtype = self.X.shape, self.X.dtype
+        self.ndim = len(self.shape)
+        self.on_device = self.ref is not None
+
+    def run_rows(self, axis, ps, step_k, c0=0, c1=None):
+        """`ps` on the two-dimensional array seen as rows of components, the components running along `axis` (1: the array as it
+        is, 0: its transpose), on components [c0, c1) of that view only"""
+        if self.on_device:
+            st = self.ref.strides if axis == 1 else self.ref.strides[::-1]
+            rows, ncol = self.shape if axis == 1 else self.shape[::-1]
+            c1 = ncol if c1 is None else min(c1, ncol)
+            _call_view(self.ref.ptr + c0 * st[1] * self.dtype.itemsize, True, self.dtype, rows, c1 - c0, st[0], st[1], ps, step_k)
+            return
+        V = self.X if axis == 1 else self.X.T
+        if c0 != 0 or (c1 is not None and c1 < V.shape[1]):
+            V = V[:, c0:c1]
+        out = _run_rows(V, ps, step_k)
+        if out is not V:
+            V[...] = out
+
+    def run_flat(self, ps, step):
+        """element-wise `ps` with the scalar `step` on every element"""
+        if self.on_device:
+            if self.ref.flat:
+                if self.ref.size:
+                    _call_flat(self.ref.ptr, True, self.dtype, self.ref.size, ps, step)
+                return
+            # a pitched two-dimensional view: its row-major orientation in groups of at most MAXK columns
+            axis = 1 if self.ref.strides[1] == 1 else 0
+            for c0 in range(0, self.shape[axis], _lib.MAXK):
+                self.run_rows(axis, ps, step, c0, c0 + _lib.MAXK)
+            return
+        Xw = self.X.T if self.X.flags.f_contiguous and not self.X.flags.c_contiguous else self.X
+        out = _run_rows(Xw.reshape(-1), ps, step)            # (a view of a contiguous array, a copy of any other)
+        if not np.may_share_memory(out, Xw):
+            Xw[...] = out.reshape(Xw.shape)
 
 
 def _scalar_or_array(thresh):
@@ -115,72 +202,61 @@ def _component_axis(shape, X_shape):
     return None
 
 
-def _apply_rows(X, step, rows, axis):
-    """One per-component table (rows[k] = (op, thresh, relative) of component k along `axis` of the 2-D X) on X in place."""
-    K = X.shape[axis]
+def _apply_rows(A, step, rows, axis):
+    """One per-component table (rows[k] = (op, thresh, relative) of component k along `axis` of the 2-D operand A) on A in place."""
+    K = A.shape[axis]
     if K > _lib.MAXK:
         raise NotImplementedError("per-component operator parameters for %d components (at most %d)" % (K, _lib.MAXK))
     if len(rows) != K:
-        raise ValueError("per-component operator parameters: %d values for %d components along axis %d of X %s" % (len(rows), K, axis, X.shape))
+        raise ValueError("per-component operator parameters: %d values for %d components along axis %d of X %s" % (len(rows), K, axis, A.shape))
     step_arr = np.asarray(step, dtype=np.float64)
     if step_arr.ndim == 0 or step_arr.size == 1:
         sk = float(step_arr.reshape(-1)[0]) if step_arr.size else 0.0
-    elif _component_axis(step_arr.shape, X.shape) == axis:
+    elif _component_axis(step_arr.shape, A.shape) == axis:
         sk = step_arr.reshape(-1)
     else:
-        raise NotImplementedError("step of shape %s next to per-component parameters along axis %d of X %s" % (step_arr.shape, axis, X.shape))
-    ps = _seq([("components", 0, rows, 0)])
-    if axis == 1:
-        X[...] = _run_rows(X, ps, sk)
-    else:
-        X[...] = _run_rows(X.T, ps, sk).T
-    return X
+        raise NotImplementedError("step of shape %s next to per-component parameters along axis %d of X %s" % (step_arr.shape, axis, A.shape))
+    A.run_rows(axis, _seq([("components", 0, rows, 0)]), sk)
+    return A.X
 
 
 def _apply(X, step, op, axis=None, thresh=0.0, kind="relative"):
-    """Run one operator on the ndarray X in place (any float dtype; computed in float32)."""
+    """Run one operator on X in place, in X's own element type (float32 and float64; any other dtype is computed in float32):
+    a host array, or an array in HBM (`__cuda_array_interface__`), which is updated where it lives.  Returns the caller's object."""
     assert kind in ["relative", "absolute"]
-    X = np.asarray(X) if not isinstance(X, np.ndarray) else X
+    A = _Operand(X)
     rel = kind == "relative"
     step_arr = np.asarray(step, dtype=np.float64)
     if op in ("unity", "unity_plus"):
-        if X.ndim != 2 or axis not in (0, 1):
+        if A.ndim != 2 or axis not in (0, 1):
             raise NotImplementedError("prox_unity on the device needs a 2-D array and axis in (0, 1)")
-        V = X if axis == 1 else X.T
-        if V.shape[1] <= _lib.MAXK:
-            out = _run_rows(V, _seq([(op, 0, 0.0, 0)]), 0.0)
-            X[...] = out if axis == 1 else out.T
-            return X
-        # long normalised axis: sums over the ROWS of the device array (column sums folded across the grid), the other axis
-        # in groups of at most MAXK independent columns
-        Wm = X if axis == 0 else X.T
-        for c0 in range(0, Wm.shape[1], _lib.MAXK):
-            Wm[:, c0:c0 + _lib.MAXK] = _run_rows(np.ascontiguousarray(Wm[:, c0:c0 + _lib.MAXK]), _seq([(op, 1, 0.0, 0)]), 0.0)
-        return X
+        if A.shape[axis] <= _lib.MAXK:
+            A.run_rows(axis, _seq([(op, 0, 0.0, 0)]), 0.0)
+            return A.X
+        # long normalised axis: sums over the ROWS of the view whose components run along the other axis (column sums folded
+        # across the grid), that axis in groups of at most MAXK independent columns
+        for c0 in range(0, A.shape[1 - axis], _lib.MAXK):
+            A.run_rows(1 - axis, _seq([(op, 1, 0.0, 0)]), 0.0, c0, c0 + _lib.MAXK)
+        return A.X
     thresh, per_k = _scalar_or_array(thresh)
     if per_k is not None:               # one threshold per component: the shapes that broadcast along X's components
-        axis = _component_axis(per_k.shape, X.shape)
+        axis = _component_axis(per_k.shape, A.shape)
         if axis is None:
             raise NotImplementedError("thresh of shape %s on X of shape %s: per-component thresholds only ((K,) / (1, K) along axis 1, "
-                                      "(K, 1) along axis 0); per-row and per-element thresholds are not built" % (per_k.shape, X.shape))
-        return _apply_rows(X, step, [(op, t, rel) for t in per_k.reshape(-1)], axis)
+                                      "(K, 1) along axis 0); per-row and per-element thresholds are not built" % (per_k.shape, A.shape))
+        return _apply_rows(A, step, [(op, t, rel) for t in per_k.reshape(-1)], axis)
     ps = _seq([(op, 0, thresh, rel)])
     if step_arr.ndim == 0 or step_arr.size == 1 or not rel or op in ("id", "zero", "plus"):
-        flat = X.reshape(-1)
-        W = _lib.MAXK
-        pad = (-flat.size) % W
-        buf = np.concatenate([flat.astype(np.float32), np.zeros(pad, np.float32)]).reshape(-1, W)
-        out = _run_rows(buf, ps, float(step_arr.reshape(-1)[0]) if step_arr.size else 0.0)
-        X[...] = out.reshape(-1)[: flat.size].reshape(X.shape)
-        return X
+        A.run_flat(ps, float(step_arr.reshape(-1)[0]) if step_arr.size else 0.0)
+        return A.X
     # per-component step (what adaprox passes: shape (K,) for A, (K,1) for S -- nmf.py:93)
-    if X.ndim == 2 and step_arr.shape in ((X.shape[1],), (1, X.shape[1])) and X.shape[1] <= _lib.MAXK:
-        X[...] = _run_rows(X, ps, step_arr.reshape(-1))
-        return X
-    if X.ndim == 2 and step_arr.shape == (X.shape[0], 1) and X.shape[0] <= _lib.MAXK:
-        X[...] = _run_rows(X.T, ps, step_arr.reshape(-1)).T
-        return X
-    raise NotImplementedError("step of shape %s does not broadcast per component over X of shape %s" % (step_arr.shape, X.shape))
+    if A.ndim == 2 and step_arr.shape in ((A.shape[1],), (1, A.shape[1])) and A.shape[1] <= _lib.MAXK:
+        A.run_rows(1, ps, step_arr.reshape(-1))
+        return A.X
+    if A.ndim == 2 and step_arr.shape == (A.shape[0], 1) and A.shape[0] <= _lib.MAXK:
+        A.run_rows(0, ps, step_arr.reshape(-1))
+        return A.X
+    raise NotImplementedError("step of shape %s does not broadcast per component over X of shape %s" % (step_arr.shape, A.shape))
 
 
 def prox_id(X, step):
@@ -269,9 +345,9 @@ def prox_max_entropy(X, step, gamma=1, type="relative"):
         gamma * step element by element -- the broadcasting the reference intends and raises on (ValueError / TypeError);
       * where gamma_ is <= 0 or NaN the entries > 0 become NaN (the reference writes NaN at 0 and numbers without
         meaning below 0)."""
-    if isinstance(X, np.ndarray) and X.dtype != np.float32:
-        # computed in float32 like every operator called on an array; the entries the operator does not touch keep their own
-        # value (not its float32 rounding): "only entries > 0 change"
+    if isinstance(X, np.ndarray) and _work_dtype(X.dtype) != X.dtype:
+        # a dtype that is computed in float32 (neither float32 nor float64): the entries the operator does not touch keep their
+        # own value, not its float32 rounding -- "only entries > 0 change"
         keep = ~(X > 0)
         kept = X[keep]
         _apply(X, step, "max_entropy", thresh=gamma, kind=type)
@@ -302,20 +378,27 @@ def prox_components(X, step, prox=None, axis=0):
     component gets it -- or a list with one callable per component (ValueError for another length).
 
     Members that are element-wise operators of this module with scalar parameters run as ONE device kernel with a
-    per-component table (2-D X, at most 128 components); any other callable is called on its component's host view.
+    per-component table (2-D X, at most 128 components); any other callable is called on its component's host view -- for an X
+    that lives on the GPU there is no such view: NotImplementedError.
     Difference from the reference's contract: a per-component `step` -- shape (K,) / (1, K) with axis=1, (K, 1) with axis=0,
     what adaprox passes -- reaches member k as component k's own step; the reference would hand every member the whole array."""
-    X = np.asarray(X) if not isinstance(X, np.ndarray) else X
-    if axis not in (0, 1) or X.ndim <= axis:
-        raise NotImplementedError("prox_components: axis %r of an array of shape %s" % (axis, X.shape))
-    K = X.shape[axis]
+    A = _Operand(X)
+    if axis not in (0, 1) or A.ndim <= axis:
+        raise NotImplementedError("prox_components: axis %r of an array of shape %s" % (axis, A.shape))
+    K = A.shape[axis]
     members = list(prox) if isinstance(prox, (list, tuple)) else [prox] * K
     if len(members) != K:
-        raise ValueError("prox_components: %d operators for %d components along axis %d of X %s" % (len(members), K, axis, X.shape))
-    if X.ndim == 2 and K <= _lib.MAXK:
+        raise ValueError("prox_components: %d operators for %d components along axis %d of X %s" % (len(members), K, axis, A.shape))
+    if A.ndim == 2 and K <= _lib.MAXK:
         rows = _component_rows(members, K)
         if rows is not None:
-            return _apply_rows(X, step, rows, axis)
+            return _apply_rows(A, step, rows, axis)
+    if A.on_device:
+        raise NotImplementedError("prox_components on an array that lives on the GPU runs as one device kernel with a per-component table: a 2-D "
+                                  "array, at most %d components, every member an element-wise operator of proxmin_amd.operators with scalar "
+                                  "parameters (got shape %s, axis %d, members %r); there is no host view to hand another callable"
+                                  % (_lib.MAXK, A.shape, axis, members))
+    X = A.X
     step_arr = np.asarray(step)
     per_k = step_arr.size > 1 and _component_axis(step_arr.shape, X.shape) == axis
     for k in range(K):
