@@ -291,11 +291,14 @@ int pmx_step_pgm(pmx_ctx* ctx, double out[2]);
 /* nmf.step_adaprox (nmf.py:91-93): out[0..K) = mean(A,0)/10, out[K..2K) = mean(S,1)/10.      */
 int pmx_step_adaprox(pmx_ctx* ctx, float* out);
 /* apply one operator to a device buffer in place, as `prox(X, step)` would (operators.py).
- * step_k: K per-component steps (scalar steps: K copies). block selects rows (M or N).        */
+ * step_k: K per-component steps (scalar steps: K copies). block selects rows (M or N).
+ * The buffer is a dense rows x K float32 view for pmx_prox_view's kernels, launched on the context's stream with the context's
+ * tables: the same bits as pmx_prox_view on a copy of the buffer.                              */
 int pmx_prox_apply(pmx_ctx* ctx, int buf, const pmx_proxseq* prox, const float* step_k);
 /* context-free variant: `prox(X, step)` on a HOST array X (rows x K float32, K <= 128, updated in
- * place): copies to the device, runs the operator kernel, copies back.  float32 and host memory only: calling
- * proxmin.operators.prox_* on an array maps to pmx_prox_view / pmx_prox_flat below, which keep the array's type and place. */
+ * place).  A float32 host wrapper of pmx_prox_view below (on_device = 0, is_f64 = 0, strides (K, 1), host_device = device, the
+ * steps widened to double): its checks, its status codes and its bits.  Calling proxmin.operators.prox_* on an array maps to
+ * pmx_prox_view / pmx_prox_flat, which keep the array's type and place. */
 int pmx_prox_array(int device, float* X, int64_t rows, int K, const pmx_proxseq* prox, const float* step_k);
 /* [ABI v7] Table `index` (0 .. PMX_MAX_TABLES - 1) of the context: K rows of the 24-byte pmx_prox, row k = the operator of
  * component k (op, thresh, relative; unit = reserved = 0).  A row is an element-wise operator: id, zero, plus, min, max, hard,
@@ -315,7 +318,7 @@ int pmx_prox_array_tables(int device, float* X, int64_t rows, int K, const pmx_p
                           const pmx_prox* tables, int ntables);
 /* [ABI v7, additive] `prox(X, step)` in the array's OWN element type and, for an array in HBM, on its own memory: what calling
  * proxmin.operators.prox_* on a float32 or float64 array maps to (the reference mutates at the array's dtype: operators.py:33-38,
- * :138-160; pmx_prox_array above is float32 and host-only and stays as it is).
+ * :138-160; pmx_prox_array / pmx_prox_array_tables above are float32 host wrappers of this entry point).
  *   X          rows x K elements of float (is_f64 = 0) or double (1), K <= 128, element (r, k) at X + r * stride0 + k * stride1 (in
  *              elements).  on_device = 0: host memory, dense and row-major (strides (K, 1)): uploaded to GPU `host_device`, updated,
  *              downloaded.  on_device = 1: device memory, updated IN PLACE, nothing copied: a row-major view (stride1 == 1, stride0 >= K:

@@ -1,10 +1,11 @@
 // Stand-alone proximal operators on the CALLER'S OWN MEMORY, in the array's element type: what `prox(X, step)` called on a float32 or
-// float64 array maps to (pmx_prox_view / pmx_prox_flat, include/pmx.h; proxmin/operators.py:20-184 mutate at the array's dtype).
+// float64 array maps to (pmx_prox_view / pmx_prox_flat, include/pmx.h; proxmin/operators.py:20-184 mutate at the array's dtype), and
+// what pmx_prox_apply / pmx_prox_array / pmx_prox_array_tables run on a context's buffer / a float32 host array.
 //
 //   k_prox_view<T, NC, ME, CM, CS> a rows x K VIEW, element (r, k) at X + r * s0 + k * s1 with one stride equal to 1 (the rule of
 //                                pmx_factor_from_device).  The operators are prox_row<T, NC, 32, ME> of k_update.hip -- the one
 //                                implementation the fp32 and fp64 solver kernels run -- so the float instance computes what
-//                                k_prox_apply<NC, ME> computes, bit for bit, and the double one what k_big_f64.hip's updates do.
+//                                the fp32 update kernels compute, bit for bit, and the double one what k_big_f64.hip's updates do.
 //                                Row r belongs to half-wave r mod 8192 of the grid (ROW_LOOP_BEGIN's mapping), NC values per lane.
 //       CM = false  s1 == 1 (row-major, any pitch): read and written in place along the components.
 //       CM = true   s0 == 1 (column-major: a K x N `S` seen as N rows of K components, or St.T): global accesses run along
@@ -14,8 +15,8 @@
 //                   bank argument for 4- and 8-byte elements).  Same rows per thread as CM = false: the column sums below agree.
 //       div / sum   prox_unity* ALONG THE ROWS (pmx_prox::unit = 1) as two launches, k_pgm_unity's scheme: `sum` leaves the
 //                   workgroup's column sums of the result in colpart (per-thread sums in row order in T, the 32 half-waves added
-//                   in double: k_colsum's), `div` opens with colsum_fold's fixed-order fold and divides every row by the totals
-//                   rounded to T (k_colscale's).  For float the result is bit for bit that of k_colsum + k_colscale.
+//                   in double: colsum_store, k_colsum's), `div` opens with colsum_totals -- colsum_fold's fixed-order fold, the
+//                   totals rounded to T -- and divides every row by them.  For float this is k_pgm_unity's arithmetic, bit for bit.
 //   k_prox_flat<T, ME>           an element-wise operator with ONE step on n contiguous elements, the tail guarded: prox_row with one
 //                                value per lane (no component structure, so no per-component tables and no prox_unity*).
 //
@@ -51,15 +52,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_prox_view(ProxViewArgs<T> a) {
     const int l32 = threadIdx.x & 31, hwi = threadIdx.x >> 5;
     const bool div = CS && a.div, sum = CS && a.sum;
     if constexpr (CS) {
-        if (div) {                           // k_colscale's fold and rounding
-            colsum_fold(a.colpart, K, false, asum);
-            if (threadIdx.x < MAXK) {
-                double t = 0.0;
-                for (int q = 0; q < ALPHA_NG; ++q) t += asum[q][threadIdx.x];
-                tot[threadIdx.x] = (T)t;
-            }
-            __syncthreads();
-        }
+        if (div) colsum_totals(a.colpart, K, asum, tot);
     }
     T cs[NC];
     bool ok[NC];
@@ -113,17 +106,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_prox_view(ProxViewArgs<T> a) {
         }
     }
     if constexpr (CS) {
-        if (sum) {                           // colsum_store in T: the 32 half-waves of the workgroup, added in order in double
-            __syncthreads();
-#pragma unroll
-            for (int c = 0; c < NC; ++c) sm[hwi * MAXK + l32 + 32 * c] = cs[c];
-            __syncthreads();
-            if (threadIdx.x < 32 * NC) {
-                double s = 0.0;
-                for (int h = 0; h < EW_THREADS / 32; ++h) s += (double)sm[h * MAXK + threadIdx.x];
-                a.colpart[(int64_t)blockIdx.x * MAXK + threadIdx.x] = s;
-            }
-        }
+        if (sum) colsum_store<NC>(cs, a.colpart, 0, sm);     // (block 0: the 32 half-waves of the workgroup, added in order in double)
     }
 }
 

@@ -510,36 +510,6 @@ __global__ __launch_bounds__(EW_THREADS) void k_fold(FoldArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// standalone prox (operators.* called on an array)
-// ------------------------------------------------------------------------------------------------
-struct ProxArgs {
-    float* X;
-    int64_t rows;
-    int K;
-    ProxSeq prox;
-    float stepk[MAXK];
-};
-template <int NC, bool ME = false>
-__global__ __launch_bounds__(EW_THREADS) void k_prox_apply(ProxArgs a) {
-    const int K = a.K;
-    ROW_LOOP_BEGIN(a.rows)
-        bool ok[NC];
-        float v[NC], sk[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int kk = l32 + 32 * c;
-            ok[c] = kk < K;
-            v[c] = ok[c] ? a.X[r * K + kk] : 0.f;
-            sk[c] = ok[c] ? a.stepk[kk] : 0.f;
-        }
-        prox_row<float, NC, 32, ME>(v, ok, a.prox, sk);
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-            if (ok[c]) a.X[r * K + l32 + 32 * c] = v[c];
-    ROW_LOOP_END
-}
-
-// ------------------------------------------------------------------------------------------------
 // PGM / FISTA update                                      (proxmin/algorithms.py:93-108,130-133)
 //   X_new = prox(Xe - s G, s);  Xe_next = X_new + omega_next (X_new - X_old)
 // ------------------------------------------------------------------------------------------------
@@ -1018,8 +988,9 @@ struct ColsumArgs {
     double* colpart;      // [2][EW_BLOCKS][MAXK]
     const DevStatus* status;
 };
-template <int NC>
-__device__ __forceinline__ void colsum_store(const float (&cs)[NC], double* colpart, int j, float* sm /* [8][MAXK] */) {
+// (T: the element type of the per-thread sums -- float in the solver kernels, the array's in k_prox_view)
+template <int NC, class T>
+__device__ __forceinline__ void colsum_store(const T (&cs)[NC], double* colpart, int j, T* sm /* [EW_THREADS / 32][MAXK] */) {
     const int hwi = threadIdx.x >> 5, l32 = threadIdx.x & 31;
     __syncthreads();
 #pragma unroll
@@ -1103,36 +1074,19 @@ __global__ __launch_bounds__(EW_THREADS) void k_alpha_init(AlphaArgs a) {
     compute_alpha(a);
 }
 
-// prox_unity / prox_unity_plus ALONG THE ROWS (numpy axis = 0 of a rows x K array: every component's column is divided
-// by its sum, operators.py:41-52), for the stand-alone operator entry points: k_colsum's per-workgroup partial column sums
-// (block 0 of `colpart`), folded here by every workgroup in colsum_fold's fixed order, then the scaling.  No zero guard,
-// like the reference.  `plus`: the projection onto the non-negative numbers comes first (it has been applied by the caller
-// before the column sums were taken); this kernel only divides.
-struct ColScaleArgs {
-    float* X;
-    int64_t rows;
-    int K;
-    const double* colpart;   // [EW_BLOCKS][MAXK]
-};
-template <int NC>
-__global__ __launch_bounds__(EW_THREADS) void k_colscale(ColScaleArgs a) {
-    __shared__ double asum[ALPHA_NG][MAXK];
-    __shared__ float tot[MAXK];
-    colsum_fold(a.colpart, a.K, false, asum);
+// The divisors of prox_unity / prox_unity_plus ALONG THE ROWS (numpy axis = 0 of a rows x K array: every component's column is
+// divided by its sum, operators.py:41-52): the per-workgroup partial column sums of block j (colsum_store's) folded by every
+// workgroup in colsum_fold's fixed order, the ALPHA_NG group sums added in order, the totals rounded to T into tot[MAXK].  No zero
+// guard, like the reference.  Ends with a barrier.  (k_pgm_unity; k_prox_view.hip for the operators called on arrays.)
+template <class T>
+__device__ __forceinline__ void colsum_totals(const double* colpart_j, int K, double (*asum)[MAXK], T* tot) {
+    colsum_fold(colpart_j, K, false, asum);
     if (threadIdx.x < MAXK) {
         double t = 0.0;
         for (int q = 0; q < ALPHA_NG; ++q) t += asum[q][threadIdx.x];
-        tot[threadIdx.x] = (float)t;
+        tot[threadIdx.x] = (T)t;
     }
     __syncthreads();
-    const int K = a.K;
-    ROW_LOOP_BEGIN(a.rows)
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int kk = l32 + 32 * c;
-            if (kk < K) a.X[r * K + kk] = a.X[r * K + kk] / tot[kk];
-        }
-    ROW_LOOP_END
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1145,8 +1099,8 @@ __global__ __launch_bounds__(EW_THREADS) void k_colscale(ColScaleArgs a) {
 //   middle  (L > 1) the previous sums folded by colsum_fold, the division, the next segment, new sums into the other half
 //           of the partials (a workgroup may still be folding the previous ones);
 //   finish  fold, division, seg_L and then all that k_pgm_update does behind its prox_row.
-// Per-thread float sums in row order and the double fold are k_colsum's / k_colscale's: the result is bit for bit what the
-// stand-alone operator gives on the same argument.  No zero guard (a column that sums to zero becomes NaN, like the
+// Per-thread float sums in row order and the double fold are those of the stand-alone operator (k_prox_view.hip: colsum_store,
+// colsum_totals): the result is bit for bit what it gives on the same argument.  No zero guard (a column that sums to zero becomes NaN, like the
 // reference's); only components < K are divided.  A block without such an entry is updated whole in the finish launch; a
 // block with fewer applications than the other idles in the middle launches it does not need.
 // ------------------------------------------------------------------------------------------------
@@ -1186,15 +1140,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_pgm_unity(PgmUnityArgs aa) {
     float* X = a.X[j];
     float* Xe = a.Xe[j];
     float* T = a.T[j];
-    if (ub.div) {                            // k_colscale's fold: the float totals of the previous application
-        colsum_fold(ub.rd + (int64_t)j * EW_BLOCKS * MAXK, K, false, asum);
-        if (threadIdx.x < MAXK) {
-            double t = 0.0;
-            for (int q = 0; q < ALPHA_NG; ++q) t += asum[q][threadIdx.x];
-            tot[threadIdx.x] = (float)t;
-        }
-        __syncthreads();
-    }
+    if (ub.div) colsum_totals(ub.rd + (int64_t)j * EW_BLOCKS * MAXK, K, asum, tot);      // the float totals of the previous application
     float cs[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) cs[c] = 0.f;
@@ -2742,7 +2688,6 @@ __global__ __launch_bounds__(EW_THREADS) void k_shard_post_split(ShardPostSplitA
     } while (0)
 
 void launch_fold(const FoldArgs& a, int nblocks_y, hipStream_t s) { DISPATCH_NC(a.K, k_fold, dim3(EW_BLOCKS, nblocks_y), s, a); }
-void launch_prox_apply(const ProxArgs& a, hipStream_t s) { DISPATCH_NC_ME(a.K, seq_has_me(a.prox), k_prox_apply, dim3(EW_BLOCKS), s, a); }
 void launch_pgm_update(const PgmArgs& a, hipStream_t s) {
     DISPATCH_NC_ME(a.K, seq_has_me(a.prox[0]) || seq_has_me(a.prox[1]), k_pgm_update, dim3(a.nbx > 0 ? a.nbx : EW_BLOCKS, 2), s, a);
 }
@@ -2757,7 +2702,6 @@ void launch_bt_finish(const BtFinishArgs& a, hipStream_t s) { hipLaunchKernelGGL
 void launch_pgm_decide(const DecideArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_pgm_decide, dim3(1), dim3(EW_THREADS), 0, s, a); }
 void launch_colsum(const ColsumArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_colsum, dim3(EW_BLOCKS, 2), s, a); }
 void launch_alpha_init(const AlphaArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_alpha_init, dim3(1), dim3(EW_THREADS), 0, s, a); }
-void launch_colscale(const ColScaleArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_colscale, dim3(EW_BLOCKS), s, a); }
 void launch_ada_moment(const MomentArgs& a, hipStream_t s) { DISPATCH_NC(a.K, k_ada_moment, dim3(EW_BLOCKS, 2), s, a); }
 #define DISPATCH_NC_NT(K, NT, ME, KERNEL, grid, stream, args)                                                      \
     do {                                                                                                           \

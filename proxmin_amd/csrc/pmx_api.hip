@@ -297,8 +297,6 @@ static bool seq_is_projection(const pmx_proxseq& p) {
     }
     return true;
 }
-// long_axis_ok: the caller has a place for prox_unity* along the rows -- the stand-alone operator entry points (pmx_prox_apply /
-// pmx_prox_array) and pmx_pgm_begin (k_pgm_unity's chain)
 static bool prox_has_max_entropy(const pmx_proxseq& p) {      // ... or a per-component table: the operators of the <.., true> instances
     for (int i = 0; i < p.n && i < PMX_MAX_SEQ; ++i)
         if (p.seq[i].op == PMX_PROX_MAX_ENTROPY || p.seq[i].op == PMX_PROX_COMPONENTS) return true;
@@ -307,7 +305,9 @@ static bool prox_has_max_entropy(const pmx_proxseq& p) {      // ... or a per-co
 static bool row_op_ok(int op) {      // what a row of a per-component table may be: the element-wise operators
     return op == PMX_PROX_ID || op == PMX_PROX_ZERO || op == PMX_PROX_PLUS || (op >= PMX_PROX_MIN && op <= PMX_PROX_MAX_ENTROPY);
 }
-// tab_set: which tables exist (pmx_ctx::tab_set), or nullptr with `ntables` of them (pmx_prox_array_tables; -1: the context has none)
+// long_axis_ok: the caller has a place for prox_unity* along the rows -- the stand-alone operator entry points (apply_prox_view) and
+// pmx_pgm_begin (k_pgm_unity's chain)
+// tab_set: which tables exist (pmx_ctx::tab_set), or nullptr with `ntables` of them (pmx_prox_view; -1: the context has none)
 static int check_prox(const pmx_proxseq& p, const char* what, bool long_axis_ok = false, const bool* tab_set = nullptr, int ntables = -1) {
     if (p.n < 0 || p.n > PMX_MAX_SEQ) FAIL(PMX_E_INVALID, "%s: bad operator count %d", what, p.n);
     for (int i = 0; i < p.n; ++i) {
@@ -329,22 +329,20 @@ static int check_prox(const pmx_proxseq& p, const char* what, bool long_axis_ok 
     return PMX_OK;
 }
 
-// one operator sequence on a rows x K device array, incl. prox_unity* along the rows (column sums over all rows).
-// `colpart` is scratch of EW_BLOCKS * MAXK doubles.
-static int apply_prox_standalone(float* X, int64_t rows, int K, const pmx_proxseq& prox, const float* step_k, double* colpart, hipStream_t stream,
-                                 const pmx_prox* tab = nullptr) {
-    bool along_rows = false;
-    for (int i = 0; i < prox.n; ++i)
-        along_rows |= (prox.seq[i].op == PMX_PROX_UNITY || prox.seq[i].op == PMX_PROX_UNITY_PLUS) && prox.seq[i].unit != 0;
-    ProxArgs a{};
-    a.X = X;
-    a.rows = rows;
-    a.K = K;
-    for (int k = 0; k < K; ++k) a.stepk[k] = step_k[k];
-    if (!along_rows) {
+// THE stand-alone operator path (k_prox_view.hip): one operator sequence on a rows x K view of device memory, element (r, k) at
+// X + r * s0 + k * s1.  The sequence, unrolled over `repeat`, is cut at prox_unity* along the rows (column sums over all rows), each
+// of them two launches.  `colpart` is scratch of EW_BLOCKS * MAXK doubles; tab: see to_dev.
+template <class T>
+static void apply_prox_view(T* X, int64_t rows, int K, int64_t s0, int64_t s1, const pmx_proxseq& prox, const double* step_k, double* colpart,
+                            const pmx_prox* tab, hipStream_t stream) {
+    ProxViewArgs<T> a{};
+    a.X = X; a.rows = rows; a.K = K; a.s0 = s0; a.s1 = s1;
+    a.colpart = colpart;
+    for (int k = 0; k < K; ++k) a.stepk[k] = (T)step_k[k];
+    if (!prox_long_axis(prox)) {
         a.prox = to_dev(prox, tab);
-        launch_prox_apply(a, stream);
-        return PMX_OK;
+        launch_prox_view<T>(a, stream);
+        return;
     }
     const int repeat = prox.repeat < 1 ? 1 : prox.repeat;
     for (int r = 0; r < repeat; ++r)
@@ -352,28 +350,22 @@ static int apply_prox_standalone(float* X, int64_t rows, int K, const pmx_proxse
             pmx_proxseq one{};
             one.n = 1; one.repeat = 1; one.seq[0] = prox.seq[i];
             const bool rows_unity = (one.seq[0].op == PMX_PROX_UNITY || one.seq[0].op == PMX_PROX_UNITY_PLUS) && one.seq[0].unit != 0;
+            a.div = 0; a.sum = 0;
             if (!rows_unity) {
                 a.prox = to_dev(one, tab);
-                launch_prox_apply(a, stream);
+                launch_prox_view<T>(a, stream);
                 continue;
             }
-            if (one.seq[0].op == PMX_PROX_UNITY_PLUS) {           // plus first (operators.py:48-52)
-                one.seq[0].op = PMX_PROX_PLUS; one.seq[0].unit = 0;
-                a.prox = to_dev(one, tab);
-                launch_prox_apply(a, stream);
-            }
-            ColsumArgs cs{};
-            cs.X[0] = X; cs.X[1] = X;
-            cs.rows[0] = rows; cs.rows[1] = 0;
-            cs.K = K;
-            cs.colpart = colpart;
-            cs.status = nullptr;
-            launch_colsum(cs, stream);
-            ColScaleArgs sc{};
-            sc.X = X; sc.rows = rows; sc.K = K; sc.colpart = colpart;
-            launch_colscale(sc, stream);
+            if (one.seq[0].op == PMX_PROX_UNITY_PLUS) { one.seq[0].op = PMX_PROX_PLUS; one.seq[0].unit = 0; }   // plus first (operators.py:48-52)
+            else one.n = 0;
+            a.prox = to_dev(one, tab);
+            a.sum = 1;
+            launch_prox_view<T>(a, stream);
+            one.n = 0;
+            a.prox = to_dev(one, tab);
+            a.sum = 0; a.div = 1;
+            launch_prox_view<T>(a, stream);
         }
-    return PMX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2080,8 +2072,10 @@ extern "C" int pmx_prox_apply(pmx_ctx* c, int buf, const pmx_proxseq* prox, cons
     float** slot; int64_t n;
     rc = buf_lookup(c, buf, &slot, &n, false);
     if (rc != PMX_OK) return rc;
-    rc = apply_prox_standalone(*slot, n / c->K, (int)c->K, *prox, step_k, c->colpart, c->stream, c->tabs);
-    if (rc != PMX_OK) return rc;
+    double sk[MAXK];                             // ((double)(float) is exact: the float instance sees these steps)
+    for (int k = 0; k < c->K; ++k) sk[k] = step_k[k];
+    // the buffer as a dense row-major view; of c->colpart ([2][EW_BLOCKS][MAXK]) block 0 is the scratch
+    apply_prox_view<float>(*slot, n / c->K, (int)c->K, c->K, 1, *prox, sk, c->colpart, c->tabs, c->stream);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(c->stream));
     return PMX_OK;
@@ -2105,46 +2099,28 @@ extern "C" int pmx_prox_table(pmx_ctx* c, int index, const pmx_prox* rows, int K
     return PMX_OK;
 }
 
-static int prox_array_impl(int device, float* X, int64_t rows, int K, const pmx_proxseq* prox, const float* step_k, const pmx_prox* tables, int ntables) {
-    if (!X || !prox || !step_k) FAIL(PMX_E_INVALID, "NULL argument");
-    if (rows <= 0 || K <= 0 || K > MAXK) FAIL(PMX_E_INVALID, "bad shape rows=%lld K=%d", (long long)rows, K);
-    if (ntables < 0 || ntables > PMX_MAX_TABLES || (ntables > 0 && !tables)) FAIL(PMX_E_INVALID, "prox_array: bad table count %d", ntables);
-    int rc = check_prox(*prox, "prox_array", true, nullptr, ntables);
-    if (rc != PMX_OK) return rc;
-    for (int64_t i = 0; i < (int64_t)ntables * K; ++i)
-        if (!row_op_ok(tables[i].op)) FAIL(PMX_E_INVALID, "prox_array: table row %lld holds op %d, which is not an element-wise operator", (long long)i, tables[i].op);
-    HIP_CHECK(hipSetDevice(device));
-    float* d = nullptr;
-    const size_t bytes = (size_t)rows * K * sizeof(float), scratch = (size_t)2 * EW_BLOCKS * MAXK * sizeof(double);
-    const size_t tabBytes = (size_t)ntables * MAXK * sizeof(pmx_prox);         // device layout: MAXK rows per table
-    HIP_CHECK(hipMalloc((void**)&d, ((bytes + 15) / 16) * 16 + scratch + tabBytes + 16));
-    double* colpart = reinterpret_cast<double*>(reinterpret_cast<char*>(d) + ((bytes + 15) / 16) * 16);
-    pmx_prox* dtab = ntables > 0 ? reinterpret_cast<pmx_prox*>(reinterpret_cast<char*>(colpart) + scratch) : nullptr;
-    hipError_t e = hipMemcpy(d, X, bytes, hipMemcpyHostToDevice);
-    for (int t = 0; t < ntables && e == hipSuccess; ++t)
-        e = hipMemcpy(dtab + (size_t)t * MAXK, tables + (size_t)t * K, sizeof(pmx_prox) * K, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = apply_prox_standalone(d, rows, K, *prox, step_k, colpart, nullptr, dtab);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpy(X, d, bytes, hipMemcpyDeviceToHost);
+// [r6] Device scratch of a context-free entry point, one block per device, kept between calls (the stepper calls pmx_bb_sums once per block
+// and iteration: a hipMalloc / hipFree pair each time cost more than the reduction); grows on demand, freed at process exit by the runtime.
+// The caller holds `mu` from get() to the end of its device work: that also serialises the null-stream work of concurrent callers on the
+// one scratch.  One instance per family of entry points: pmx_bb_sums does not wait for an operator call, nor the other way round.
+struct DeviceScratch {
+    std::mutex mu;
+    struct { char* d = nullptr; size_t bytes = 0; } dev[16];
+    int get(int device, size_t need, char** out) {       // (mu held)
+        auto& sc = dev[device];
+        if (sc.bytes < need) {
+            if (sc.d) (void)hipFree(sc.d);
+            sc.d = nullptr;
+            sc.bytes = 0;
+            HIP_CHECK(hipMalloc((void**)&sc.d, need));
+            sc.bytes = need;
+        }
+        *out = sc.d;
+        return PMX_OK;
     }
-    (void)hipFree(d);
-    if (e != hipSuccess) FAIL(PMX_E_HIP, "prox_array: %s", hipGetErrorString(e));
-    return PMX_OK;
-}
-extern "C" int pmx_prox_array(int device, float* X, int64_t rows, int K, const pmx_proxseq* prox, const float* step_k) {
-    return prox_array_impl(device, X, rows, K, prox, step_k, nullptr, 0);
-}
-extern "C" int pmx_prox_array_tables(int device, float* X, int64_t rows, int K, const pmx_proxseq* prox, const float* step_k,
-                                     const pmx_prox* tables, int ntables) {
-    return prox_array_impl(device, X, rows, K, prox, step_k, tables, ntables);
-}
-
-// [r6] scratch of pmx_bb_sums, one per device, kept between calls (the stepper calls this once per block and iteration: a hipMalloc / hipFree
-// pair each time cost more than the reduction); grows on demand, freed at process exit by the runtime
-struct BbScratch { char* d = nullptr; size_t bytes = 0; };
-static std::mutex g_bb_mu;
-static BbScratch g_bb_scratch[16];
+};
+static DeviceScratch g_bb_scratch;       // pmx_bb_sums
+static DeviceScratch g_pv_scratch;       // the operators called on arrays (pmx_prox_view, pmx_prox_flat, pmx_prox_array*)
 extern "C" int pmx_bb_sums(int device, int is_f64, const void* X, const void* Xprev, const void* G, const void* Gprev, int64_t count, double out[6]) {
     if (!X || !G || !out) FAIL(PMX_E_INVALID, "NULL argument");
     if (count <= 0) FAIL(PMX_E_INVALID, "bad count %lld", (long long)count);
@@ -2154,16 +2130,10 @@ extern "C" int pmx_bb_sums(int device, int is_f64, const void* X, const void* Xp
     const size_t es = is_f64 ? sizeof(double) : sizeof(float), bytes = ((size_t)count * es + 15) / 16 * 16;
     const int narr = Xprev ? 4 : 2;
     const size_t need = narr * bytes + (BBS_BLOCKS * 6 + 6) * sizeof(double);
-    std::lock_guard<std::mutex> lock(g_bb_mu);           // (also serialises the null-stream work of concurrent callers on the one scratch)
-    BbScratch& sc = g_bb_scratch[device];
-    if (sc.bytes < need) {
-        if (sc.d) (void)hipFree(sc.d);
-        sc.d = nullptr;
-        sc.bytes = 0;
-        HIP_CHECK(hipMalloc((void**)&sc.d, need));
-        sc.bytes = need;
-    }
-    char* d = sc.d;
+    std::lock_guard<std::mutex> lock(g_bb_scratch.mu);
+    char* d;
+    int rc = g_bb_scratch.get(device, need, &d);
+    if (rc != PMX_OK) return rc;
     const void* src[4] = {X, G, Xprev, Gprev};
     hipError_t e = hipSuccess;
     for (int i = 0; i < narr && e == hipSuccess; ++i) e = hipMemcpy(d + i * bytes, src[i], (size_t)count * es, hipMemcpyHostToDevice);
@@ -2184,26 +2154,10 @@ extern "C" int pmx_bb_sums(int device, int is_f64, const void* X, const void* Xp
 // ------------------------------------------------------------------------------------------------
 // operators called on arrays, in the array's type and on the array's own memory (k_prox_view.hip)
 // ------------------------------------------------------------------------------------------------
-// scratch of pmx_prox_view / pmx_prox_flat, one per device, kept between calls like pmx_bb_sums's: the column-sum partials, the
-// per-component tables (device layout: MAXK rows each) and, for host arrays only, the dense copy of the array
-struct PvScratch { char* d = nullptr; size_t bytes = 0; };
-static std::mutex g_pv_mu;
-static PvScratch g_pv_scratch[16];
+// g_pv_scratch holds the column-sum partials, the per-component tables (device layout: MAXK rows each) and, for host arrays only, the
+// dense copy of the array
 constexpr size_t PV_COLPART_BYTES = (size_t)EW_BLOCKS * MAXK * sizeof(double);
 constexpr size_t PV_TABLE_BYTES = (size_t)PMX_MAX_TABLES * MAXK * sizeof(pmx_prox);
-static int pv_scratch(int device, size_t data_bytes, char** out) {      // (g_pv_mu held)
-    const size_t need = PV_COLPART_BYTES + PV_TABLE_BYTES + data_bytes;
-    PvScratch& sc = g_pv_scratch[device];
-    if (sc.bytes < need) {
-        if (sc.d) (void)hipFree(sc.d);
-        sc.d = nullptr;
-        sc.bytes = 0;
-        HIP_CHECK(hipMalloc((void**)&sc.d, need));
-        sc.bytes = need;
-    }
-    *out = sc.d;
-    return PMX_OK;
-}
 // the calling thread's current device, put back when the entry point returns: an operator call on a tensor of another GPU must not
 // move where the caller's next allocation lands
 struct DeviceRestore {
@@ -2228,64 +2182,15 @@ extern "C" int pmx_pointer_device(const void* dptr, int* device) {
     return pointer_device(dptr, device);
 }
 
-// one operator sequence on a view: apply_prox_standalone's cut at prox_unity* along the rows, each of them two launches
-template <class T>
-static void apply_prox_view(T* X, int64_t rows, int K, int64_t s0, int64_t s1, const pmx_proxseq& prox, const double* step_k, double* colpart,
-                            const pmx_prox* tab, hipStream_t stream) {
-    ProxViewArgs<T> a{};
-    a.X = X; a.rows = rows; a.K = K; a.s0 = s0; a.s1 = s1;
-    a.colpart = colpart;
-    for (int k = 0; k < K; ++k) a.stepk[k] = (T)step_k[k];
-    if (!prox_long_axis(prox)) {
-        a.prox = to_dev(prox, tab);
-        launch_prox_view<T>(a, stream);
-        return;
-    }
-    const int repeat = prox.repeat < 1 ? 1 : prox.repeat;
-    for (int r = 0; r < repeat; ++r)
-        for (int i = 0; i < prox.n; ++i) {
-            pmx_proxseq one{};
-            one.n = 1; one.repeat = 1; one.seq[0] = prox.seq[i];
-            const bool rows_unity = (one.seq[0].op == PMX_PROX_UNITY || one.seq[0].op == PMX_PROX_UNITY_PLUS) && one.seq[0].unit != 0;
-            a.div = 0; a.sum = 0;
-            if (!rows_unity) {
-                a.prox = to_dev(one, tab);
-                launch_prox_view<T>(a, stream);
-                continue;
-            }
-            if (one.seq[0].op == PMX_PROX_UNITY_PLUS) { one.seq[0].op = PMX_PROX_PLUS; one.seq[0].unit = 0; }   // plus first (operators.py:48-52)
-            else one.n = 0;
-            a.prox = to_dev(one, tab);
-            a.sum = 1;
-            launch_prox_view<T>(a, stream);
-            one.n = 0;
-            a.prox = to_dev(one, tab);
-            a.sum = 0; a.div = 1;
-            launch_prox_view<T>(a, stream);
-        }
-}
-
-extern "C" int pmx_prox_view(void* X, int on_device, int is_f64, int64_t rows, int K, int64_t stride0, int64_t stride1, const pmx_proxseq* prox,
-                             const double* step_k, const pmx_prox* tables, int ntables, int host_device) {
-    if (!X || !prox || !step_k) FAIL(PMX_E_INVALID, "NULL argument");
-    if (rows <= 0 || K <= 0 || K > MAXK) FAIL(PMX_E_INVALID, "prox_view: bad shape rows=%lld K=%d (K <= %d)", (long long)rows, K, MAXK);
-    const size_t es = is_f64 ? sizeof(double) : sizeof(float);
-    if (reinterpret_cast<uintptr_t>(X) % es) FAIL(PMX_E_INVALID, "prox_view: %p is not aligned to its %zu-byte elements", X, es);
-    const bool rowmajor = (stride1 == 1 || K == 1) && (stride0 >= K || rows == 1), colmajor = (stride0 == 1 || rows == 1) && (stride1 >= rows || K == 1);
-    if (!rowmajor && !colmajor)
-        FAIL(PMX_E_INVALID, "prox_view: strides (%lld, %lld) of a %lld x %d view: one of them must be 1 and the other at least the extent it steps over",
-             (long long)stride0, (long long)stride1, (long long)rows, K);
-    if (!on_device && !(stride1 == 1 && stride0 == K)) FAIL(PMX_E_INVALID, "prox_view: a host array is dense and row-major (strides (K, 1))");
-    if (ntables < 0 || ntables > PMX_MAX_TABLES || (ntables > 0 && !tables)) FAIL(PMX_E_INVALID, "prox_view: bad table count %d", ntables);
-    int rc = check_prox(*prox, "prox_view", true, nullptr, ntables);
-    if (rc != PMX_OK) return rc;
-    for (int64_t i = 0; i < (int64_t)ntables * K; ++i)
-        if (!row_op_ok(tables[i].op)) FAIL(PMX_E_INVALID, "prox_view: table row %lld holds op %d, which is not an element-wise operator", (long long)i, tables[i].op);
-    // (an axis of extent 1 is never stepped along: its stride does not count)
-    const int64_t s0 = rowmajor ? (rows > 1 ? stride0 : K) : 1, s1 = rowmajor ? 1 : (K > 1 ? stride1 : rows);
+// What every operator call on an array does around its launches.  Before: the device of the pointer (on_device) or `host_device`,
+// made current until the entry point returns; the scratch; the tables and a host array (host_bytes of it) uploaded.  Then
+// run(array on the device, colpart, tables on the device or nullptr) enqueues on the null stream.  After: a host array downloaded, a
+// device array complete when the call returns.
+template <class Run>
+static int on_array(const char* what, void* X, int on_device, size_t host_bytes, int K, const pmx_prox* tables, int ntables, int host_device, Run run) {
     int device = host_device;
     if (on_device) {
-        rc = pointer_device(X, &device);
+        const int rc = pointer_device(X, &device);
         if (rc != PMX_OK) return rc;
     }
     if (device < 0 || device >= 16) FAIL(PMX_E_INVALID, "bad device %d", device);
@@ -2294,12 +2199,11 @@ extern "C" int pmx_prox_view(void* X, int on_device, int is_f64, int64_t rows, i
     // The array interface that hands a device pointer over carries no stream: everything enqueued on ANY stream of this device
     // before the call is finished first (pmx_factor_from_device's rule); the work is complete when the call returns.
     if (on_device) HIP_CHECK(hipDeviceSynchronize());
-    std::lock_guard<std::mutex> lock(g_pv_mu);           // (also serialises the null-stream work of concurrent callers on the one scratch)
-    const size_t bytes = on_device ? 0 : (size_t)rows * K * es;
+    std::lock_guard<std::mutex> lock(g_pv_scratch.mu);
+    const size_t bytes = on_device ? 0 : host_bytes;
     char* d;
-    rc = pv_scratch(device, bytes, &d);
+    const int rc = g_pv_scratch.get(device, PV_COLPART_BYTES + PV_TABLE_BYTES + bytes, &d);
     if (rc != PMX_OK) return rc;
-    double* colpart = reinterpret_cast<double*>(d);
     pmx_prox* dtab = ntables > 0 ? reinterpret_cast<pmx_prox*>(d + PV_COLPART_BYTES) : nullptr;
     void* arr = on_device ? X : (void*)(d + PV_COLPART_BYTES + PV_TABLE_BYTES);
     hipError_t e = hipSuccess;
@@ -2307,13 +2211,55 @@ extern "C" int pmx_prox_view(void* X, int on_device, int is_f64, int64_t rows, i
         e = hipMemcpy(dtab + (size_t)t * MAXK, tables + (size_t)t * K, sizeof(pmx_prox) * K, hipMemcpyHostToDevice);
     if (e == hipSuccess && !on_device) e = hipMemcpy(arr, X, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        if (is_f64) apply_prox_view<double>((double*)arr, rows, K, s0, s1, *prox, step_k, colpart, dtab, nullptr);
-        else apply_prox_view<float>((float*)arr, rows, K, s0, s1, *prox, step_k, colpart, dtab, nullptr);
+        run(arr, reinterpret_cast<double*>(d), dtab);
         e = hipGetLastError();
         if (e == hipSuccess) e = on_device ? hipStreamSynchronize(nullptr) : hipMemcpy(X, arr, bytes, hipMemcpyDeviceToHost);
     }
-    if (e != hipSuccess) FAIL(PMX_E_HIP, "prox_view: %s", hipGetErrorString(e));
+    if (e != hipSuccess) FAIL(PMX_E_HIP, "%s: %s", what, hipGetErrorString(e));
     return PMX_OK;
+}
+
+// pmx_prox_view, and pmx_prox_array / pmx_prox_array_tables through it; `what` names the entry point in the error texts.  Every
+// refusal comes before any device work and leaves X untouched.
+static int prox_view_impl(const char* what, void* X, int on_device, int is_f64, int64_t rows, int K, int64_t stride0, int64_t stride1,
+                          const pmx_proxseq* prox, const double* step_k, const pmx_prox* tables, int ntables, int host_device) {
+    if (!X || !prox || !step_k) FAIL(PMX_E_INVALID, "NULL argument");
+    if (rows <= 0 || K <= 0 || K > MAXK) FAIL(PMX_E_INVALID, "%s: bad shape rows=%lld K=%d (K <= %d)", what, (long long)rows, K, MAXK);
+    const size_t es = is_f64 ? sizeof(double) : sizeof(float);
+    if (reinterpret_cast<uintptr_t>(X) % es) FAIL(PMX_E_INVALID, "%s: %p is not aligned to its %zu-byte elements", what, X, es);
+    const bool rowmajor = (stride1 == 1 || K == 1) && (stride0 >= K || rows == 1), colmajor = (stride0 == 1 || rows == 1) && (stride1 >= rows || K == 1);
+    if (!rowmajor && !colmajor)
+        FAIL(PMX_E_INVALID, "%s: strides (%lld, %lld) of a %lld x %d view: one of them must be 1 and the other at least the extent it steps over",
+             what, (long long)stride0, (long long)stride1, (long long)rows, K);
+    if (!on_device && !(stride1 == 1 && stride0 == K)) FAIL(PMX_E_INVALID, "%s: a host array is dense and row-major (strides (K, 1))", what);
+    if (ntables < 0 || ntables > PMX_MAX_TABLES || (ntables > 0 && !tables)) FAIL(PMX_E_INVALID, "%s: bad table count %d", what, ntables);
+    const int rc = check_prox(*prox, what, true, nullptr, ntables);
+    if (rc != PMX_OK) return rc;
+    for (int64_t i = 0; i < (int64_t)ntables * K; ++i)
+        if (!row_op_ok(tables[i].op)) FAIL(PMX_E_INVALID, "%s: table row %lld holds op %d, which is not an element-wise operator", what, (long long)i, tables[i].op);
+    // (an axis of extent 1 is never stepped along: its stride does not count)
+    const int64_t s0 = rowmajor ? (rows > 1 ? stride0 : K) : 1, s1 = rowmajor ? 1 : (K > 1 ? stride1 : rows);
+    return on_array(what, X, on_device, (size_t)rows * K * es, K, tables, ntables, host_device, [&](void* arr, double* colpart, const pmx_prox* dtab) {
+        if (is_f64) apply_prox_view<double>((double*)arr, rows, K, s0, s1, *prox, step_k, colpart, dtab, nullptr);
+        else apply_prox_view<float>((float*)arr, rows, K, s0, s1, *prox, step_k, colpart, dtab, nullptr);
+    });
+}
+extern "C" int pmx_prox_view(void* X, int on_device, int is_f64, int64_t rows, int K, int64_t stride0, int64_t stride1, const pmx_proxseq* prox,
+                             const double* step_k, const pmx_prox* tables, int ntables, int host_device) {
+    return prox_view_impl("prox_view", X, on_device, is_f64, rows, K, stride0, stride1, prox, step_k, tables, ntables, host_device);
+}
+// the float32 host wrappers of pmx_prox_view: a dense rows x K host array, float steps ((double)(float) is exact)
+static int prox_array_f32(int device, float* X, int64_t rows, int K, const pmx_proxseq* prox, const float* step_k, const pmx_prox* tables, int ntables) {
+    double sk[MAXK];
+    for (int k = 0; step_k && k < K && k < MAXK; ++k) sk[k] = step_k[k];
+    return prox_view_impl("prox_array", X, 0, 0, rows, K, K, 1, prox, step_k ? sk : nullptr, tables, ntables, device);
+}
+extern "C" int pmx_prox_array(int device, float* X, int64_t rows, int K, const pmx_proxseq* prox, const float* step_k) {
+    return prox_array_f32(device, X, rows, K, prox, step_k, nullptr, 0);
+}
+extern "C" int pmx_prox_array_tables(int device, float* X, int64_t rows, int K, const pmx_proxseq* prox, const float* step_k,
+                                     const pmx_prox* tables, int ntables) {
+    return prox_array_f32(device, X, rows, K, prox, step_k, tables, ntables);
 }
 
 extern "C" int pmx_prox_flat(void* X, int on_device, int is_f64, int64_t n, const pmx_proxseq* prox, double step, int host_device) {
@@ -2321,27 +2267,11 @@ extern "C" int pmx_prox_flat(void* X, int on_device, int is_f64, int64_t n, cons
     if (n <= 0) FAIL(PMX_E_INVALID, "prox_flat: bad count %lld", (long long)n);
     const size_t es = is_f64 ? sizeof(double) : sizeof(float);
     if (reinterpret_cast<uintptr_t>(X) % es) FAIL(PMX_E_INVALID, "prox_flat: %p is not aligned to its %zu-byte elements", X, es);
-    int rc = check_prox(*prox, "prox_flat", true, nullptr, 0);
+    const int rc = check_prox(*prox, "prox_flat", true, nullptr, 0);
     if (rc != PMX_OK) return rc;
     for (int i = 0; i < prox->n; ++i)
         if (!row_op_ok(prox->seq[i].op)) FAIL(PMX_E_INVALID, "prox_flat: op %d is not an element-wise operator", prox->seq[i].op);
-    int device = host_device;
-    if (on_device) {
-        rc = pointer_device(X, &device);
-        if (rc != PMX_OK) return rc;
-    }
-    if (device < 0 || device >= 16) FAIL(PMX_E_INVALID, "bad device %d", device);
-    DeviceRestore restore;
-    HIP_CHECK(hipSetDevice(device));
-    if (on_device) HIP_CHECK(hipDeviceSynchronize());
-    std::lock_guard<std::mutex> lock(g_pv_mu);
-    const size_t bytes = on_device ? 0 : (size_t)n * es;
-    char* d;
-    rc = pv_scratch(device, bytes, &d);
-    if (rc != PMX_OK) return rc;
-    void* arr = on_device ? X : (void*)(d + PV_COLPART_BYTES + PV_TABLE_BYTES);
-    hipError_t e = on_device ? hipSuccess : hipMemcpy(arr, X, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
+    return on_array("prox_flat", X, on_device, (size_t)n * es, 0, nullptr, 0, host_device, [&](void* arr, double*, const pmx_prox*) {
         if (is_f64) {
             ProxFlatArgs<double> a{(double*)arr, n, to_dev(*prox, nullptr), step};
             launch_prox_flat<double>(a, nullptr);
@@ -2349,11 +2279,7 @@ extern "C" int pmx_prox_flat(void* X, int on_device, int is_f64, int64_t n, cons
             ProxFlatArgs<float> a{(float*)arr, n, to_dev(*prox, nullptr), (float)step};
             launch_prox_flat<float>(a, nullptr);
         }
-        e = hipGetLastError();
-        if (e == hipSuccess) e = on_device ? hipStreamSynchronize(nullptr) : hipMemcpy(X, arr, bytes, hipMemcpyDeviceToHost);
-    }
-    if (e != hipSuccess) FAIL(PMX_E_HIP, "prox_flat: %s", hipGetErrorString(e));
-    return PMX_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,9 +1,9 @@
 """GPU: the remaining sites of the per-component operators (PMX_PROX_COMPONENTS, op 12) -- tests/test_gpu_components.py has the
 update kernels proper.
 
-* `DeviceNMF.prox_apply` (pmx_prox_apply with the context's tables): equal rows are the scalar operator, distinct rows and a mixed
-  prox_components are the stand-alone call on an ndarray (which that file checks column by column), bit for bit; its tables go
-  into the slots BEHIND those of the running solver, whose next iterations are unchanged.
+* `DeviceNMF.prox_apply` (pmx_prox_apply with the context's tables: k_prox_view on the context's buffer): equal rows are the
+  scalar operator, distinct rows and a mixed prox_components are the stand-alone call on an ndarray (which that file checks column
+  by column), bit for bit; its tables go into the slots BEHIND those of the running solver, whose next iterations are unchanged.
 * pgm / FISTA with op 12 beside prox_unity* along a factor's long axis in ONE sequence (k_pgm_unity's chain): equal rows are the
   scalar sequence, distinct rows are the same call on the host route (the stand-alone kernels between launches), bit for bit.
 * the line search (k_bt_update; at 256 x 512 x 64 the K = 64 whole-block kernels, k64b_bt_update) and pgm with step arrays

@@ -11,7 +11,7 @@ float32 arithmetic, which is what the update chain computes in; the split-precis
 separately tested error.  The library's default arithmetic is covered by the bit-for-bit comparison below.
 
 Bit for bit.  The same call with the operator wrapped in a Python function is the host route -- T = Xe - s G downloaded, the
-stand-alone k_colsum + k_colscale on a fresh upload, the result uploaded again -- and must give IDENTICAL factors.
+stand-alone k_prox_view (its `sum` and `div` launches) on a fresh upload, the result uploaded again -- and must give IDENTICAL factors.
 
 Shapes are the smallest that reach each path: the small front (260 x 380 x 6), NC = 2 with a ragged K (700 x 96 x 33), a
 second row sweep of the 8192-row grid on A (8225 x 64 x 64) and on S with K = 40 (96 x 8232 x 40: a K without a tuned gradient
