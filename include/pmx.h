@@ -531,6 +531,44 @@ int pmx_comm_reduce_scatter(pmx_ctx* ctx, const float* dsend, float* drecv, int6
 int pmx_comm_all_gather(pmx_ctx* ctx, const float* dsend, float* drecv, int64_t sendcount);             /* drecv: world x sendcount */
 int pmx_comm_destroy(pmx_ctx* ctx);
 
+/* ---- batches of small problems [ABI v7, additive] ------------------------------------------------------------------------
+ * B independent factorisations Y_b ~ A_b S_b in ONE launch: for each of them what the reference's nmf() does with algorithm=pgm --
+ * the closure set-up of nmf.py:150-162 and the whole loop of algorithms.py:87-135 (gradient, Lipschitz steps, proximal update,
+ * Nesterov extrapolation, the stopping test), every problem up to ITS OWN stop or max_iter -- without a context per problem and
+ * without a launch chain per iteration (csrc/k_batch.hip: one workgroup runs a whole solve and then draws the next problem).
+ * Context-free, like pmx_prox_view: allocates on `device`, uploads the packed batch, launches, downloads, frees; the calling
+ * thread's current device is put back.  Float32 only; the results are those of B single pmx_pgm_run calls bit for bit.
+ *   items   per problem its shape and where it sits in the three packed host arrays, offsets in floats: Y_b is M x N with row pitch
+ *           ldY >= N at Y + offY; A_b is M x K, dense, at A + offA; S_b is K x N, dense, IN THE REFERENCE'S ORIENTATION, at S + offS
+ *           (transposed to the kernels' N x K inside the call).  The problems' regions must not overlap.  A and S are updated in place,
+ *           and only when the call succeeds.
+ *   limits  1 <= K <= 16, M <= 4096, N <= 8192, M N <= 2^20 (where both small-problem device bodies apply): PMX_E_INVALID outside,
+ *           as for a NULL argument, B < 0, negative offsets or ldY < N.  B == 0 does nothing.
+ *   p       prox[j] as in pmx_pgm_params, common to the batch: the operators that act within a row with scalar parameters.
+ *           PMX_E_UNSUPPORTED for prox_unity* along the rows (unit = 1), PMX_PROX_MAX_ENTROPY and PMX_PROX_COMPONENTS.
+ *           step_scale multiplies the Lipschitz steps (rounded to float, as pmx_pgm_params carries it); use_fixed_steps = 1 takes
+ *           fixed_steps[] instead.  accelerated, e_rel, max_iter as in pgm.  max_workgroups > 0 caps the grid; 0: as many
+ *           workgroups as are resident on the device.
+ *   out     per problem: iterations done, whether its test fired, the last per-block verdicts, the last steps and the two sums
+ *           [block][diff^2, norm^2] of the last test.
+ * A packed batch that does not fit in free device memory fails with PMX_E_NOMEM; splitting it is the caller's business. */
+typedef struct pmx_batch_item { int64_t M, N; int32_t K, pad; int64_t ldY, offY, offA, offS; } pmx_batch_item;
+typedef struct pmx_batch_result { int32_t it_done, stopped, conv[2]; double step[2]; double norms[2][2]; } pmx_batch_result;
+typedef struct pmx_batch_params {
+    pmx_proxseq prox[2];
+    double e_rel[2];
+    double step_scale;
+    double fixed_steps[2];
+    int32_t use_fixed_steps, accelerated, max_iter, max_workgroups;
+} pmx_batch_params;
+int pmx_nmf_batch_pgm(int device, int64_t B, const pmx_batch_item* items, const float* Y, float* A, float* S,
+                      const pmx_batch_params* p, pmx_batch_result* out);
+/* sizeof of the three structs above, in that order (pmx_abi_sizes keeps its five) */
+int pmx_batch_abi_sizes(int sizes[3]);
+/* duration in ms (HIP events) of the kernel launches of this thread's last successful pmx_nmf_batch_pgm, transfers and
+ * allocations excluded: for measurements */
+int pmx_batch_last_launch_ms(double* ms);
+
 #ifdef __cplusplus
 }
 #endif

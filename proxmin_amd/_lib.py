@@ -62,6 +62,20 @@ class BsdmmParams(C.Structure):
                 ("e_rel", C.c_double * 2), ("e_abs", C.c_double * 2), ("n_order", C.c_int32), ("order", C.c_int32 * 8)]
 
 
+class BatchItem(C.Structure):          # pmx_batch_item: one problem of pmx_nmf_batch_pgm, offsets in floats into the packed Y / A / S
+    _fields_ = [("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int32), ("pad", C.c_int32),
+                ("ldY", C.c_int64), ("offY", C.c_int64), ("offA", C.c_int64), ("offS", C.c_int64)]
+
+
+class BatchResult(C.Structure):
+    _fields_ = [("it_done", C.c_int32), ("stopped", C.c_int32), ("conv", C.c_int32 * 2), ("step", C.c_double * 2), ("norms", (C.c_double * 2) * 2)]
+
+
+class BatchParams(C.Structure):
+    _fields_ = [("prox", ProxSeq * 2), ("e_rel", C.c_double * 2), ("step_scale", C.c_double), ("fixed_steps", C.c_double * 2),
+                ("use_fixed_steps", C.c_int32), ("accelerated", C.c_int32), ("max_iter", C.c_int32), ("max_workgroups", C.c_int32)]
+
+
 _SIGNATURES = {
     "pmx_abi_version": (C.c_int, []),
     "pmx_last_error": (C.c_char_p, []),
@@ -137,6 +151,10 @@ _SIGNATURES = {
     "pmx_comm_reduce_scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "pmx_comm_all_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "pmx_comm_destroy": (C.c_int, [C.c_void_p]),
+    "pmx_nmf_batch_pgm": (C.c_int, [C.c_int, C.c_int64, C.POINTER(BatchItem), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BatchParams),
+                                    C.POINTER(BatchResult)]),
+    "pmx_batch_abi_sizes": (C.c_int, [C.POINTER(C.c_int)]),
+    "pmx_batch_last_launch_ms": (C.c_int, [C.POINTER(C.c_double)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -189,6 +207,11 @@ def load():
     mine = [C.sizeof(t) for t in (ProxSeq, PgmParams, AdaproxParams, BsdmmParams, Result)]
     if list(sizes) != mine:
         raise PmxError("struct layouts of libpmx.so %r differ from the ctypes mirrors %r; rebuild" % (list(sizes), mine))
+    sizes = (C.c_int * 3)()
+    lib.pmx_batch_abi_sizes(sizes)
+    mine = [C.sizeof(t) for t in (BatchItem, BatchResult, BatchParams)]
+    if list(sizes) != mine:
+        raise PmxError("batch struct layouts of libpmx.so %r differ from the ctypes mirrors %r; rebuild" % (list(sizes), mine))
     _lib = lib
     return lib
 

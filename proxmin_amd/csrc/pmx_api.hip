@@ -37,6 +37,7 @@
 #include "k_big_f64.hip"
 #include "k_xfer.hip"
 #include "k_prox_view.hip"
+#include "k_batch.hip"
 
 // ------------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -2280,6 +2281,214 @@ extern "C" int pmx_prox_flat(void* X, int on_device, int is_f64, int64_t n, cons
             launch_prox_flat<float>(a, nullptr);
         }
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// batches of small problems: pgm / FISTA of B problems in one launch per K bucket (k_batch.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" int pmx_batch_abi_sizes(int sizes[3]) {
+    if (!sizes) FAIL(PMX_E_INVALID, "NULL argument");
+    sizes[0] = (int)sizeof(pmx_batch_item);
+    sizes[1] = (int)sizeof(pmx_batch_result);
+    sizes[2] = (int)sizeof(pmx_batch_params);
+    return PMX_OK;
+}
+static thread_local double g_batch_launch_ms = 0.0;
+extern "C" int pmx_batch_last_launch_ms(double* ms) {
+    if (!ms) FAIL(PMX_E_INVALID, "NULL argument");
+    *ms = g_batch_launch_ms;
+    return PMX_OK;
+}
+// device allocations of one call, freed on every way out
+struct BatchBufs {
+    std::vector<void*> p;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~BatchBufs() {
+        for (void* q : p) (void)hipFree(q);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+    template <class T>
+    int get(T** out, size_t count) {
+        void* q = nullptr;
+        const size_t bytes = count * sizeof(T);
+        const hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
+        if (e != hipSuccess) { (void)hipGetLastError(); FAIL(PMX_E_NOMEM, "nmf_batch: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); }
+        p.push_back(q);
+        *out = static_cast<T*>(q);
+        return PMX_OK;
+    }
+};
+// everything the Python layer refuses as well, before the device is touched
+static int batch_check(int device, int64_t B, const pmx_batch_item* items, const float* Y, float* A, float* S, const pmx_batch_params* p, pmx_batch_result* out) {
+    if (B < 0) FAIL(PMX_E_INVALID, "nmf_batch: B = %lld", (long long)B);
+    if (!p) FAIL(PMX_E_INVALID, "nmf_batch: params is NULL");
+    if (B > 0 && (!items || !Y || !A || !S || !out)) FAIL(PMX_E_INVALID, "nmf_batch: NULL argument");
+    if (B > (int64_t)1 << 30) FAIL(PMX_E_INVALID, "nmf_batch: B = %lld", (long long)B);
+    if (device < 0 || device >= 16) FAIL(PMX_E_INVALID, "bad device %d", device);
+    if (p->max_iter < 0 || p->max_workgroups < 0) FAIL(PMX_E_INVALID, "nmf_batch: max_iter and max_workgroups are >= 0");
+    for (int j = 0; j < 2; ++j) {
+        if (p->prox[j].n >= 0 && p->prox[j].n <= PMX_MAX_SEQ && prox_has_max_entropy(p->prox[j]))
+            FAIL(PMX_E_UNSUPPORTED, "nmf_batch: %s: prox_max_entropy and per-component tables are not in the batch kernel (loop over the single call)", j ? "prox_S" : "prox_A");
+        const int rc = check_prox(p->prox[j], j ? "nmf_batch: prox_S" : "nmf_batch: prox_A", false, nullptr, 0);
+        if (rc != PMX_OK) return rc;
+    }
+    for (int64_t b = 0; b < B; ++b) {
+        const pmx_batch_item& q = items[b];
+        if (q.K < 1 || q.K > SG_KMAX || q.M < 1 || q.M > 4096 || q.N < 1 || q.N > 8192 || q.M * q.N > ((int64_t)1 << 20))
+            FAIL(PMX_E_INVALID, "nmf_batch: problem %lld is %lld x %lld x %d: a batch takes K <= 16, M <= 4096, N <= 8192, M N <= 2^20", (long long)b,
+                 (long long)q.M, (long long)q.N, q.K);
+        if (q.ldY < q.N || q.offY < 0 || q.offA < 0 || q.offS < 0)
+            FAIL(PMX_E_INVALID, "nmf_batch: problem %lld: ldY %lld < N or a negative offset", (long long)b, (long long)q.ldY);
+    }
+    return PMX_OK;
+}
+
+template <int KM>
+static int batch_slots(int cus, int* slots) {
+    int per = 0;
+    HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_batch_pgm<KM>, 256, 0));
+    *slots = (per < 1 ? 1 : per) * cus;
+    return PMX_OK;
+}
+
+extern "C" int pmx_nmf_batch_pgm(int device, int64_t B, const pmx_batch_item* items, const float* Y, float* A, float* S,
+                                 const pmx_batch_params* p, pmx_batch_result* out) {
+    int rc = batch_check(device, B, items, Y, A, S, p, out);
+    if (rc != PMX_OK) return rc;
+    if (B == 0) return PMX_OK;
+    DeviceRestore restore;
+    HIP_CHECK(hipSetDevice(device));
+    int cus = 0;
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    // extents of the packed arrays; the two K buckets (grad_small_tile / eig_small_body are unrolled to KM = 8 or 16, and the single call
+    // picks by K <= 8), each ordered largest first
+    int64_t nY = 0, nA = 0, nS = 0;
+    std::vector<int> order[2];
+    int64_t slabFloats = 1;
+    int lossSlots = 1;
+    for (int64_t b = 0; b < B; ++b) {
+        const pmx_batch_item& q = items[b];
+        nY = std::max(nY, q.offY + (q.M - 1) * q.ldY + q.N);
+        nA = std::max(nA, q.offA + q.M * q.K);
+        nS = std::max(nS, q.offS + q.N * q.K);
+        order[q.K <= 8 ? 0 : 1].push_back((int)b);
+        const int64_t tx = (q.N + SG_COLS - 1) / SG_COLS, ty = (q.M + SG_ROWS - 1) / SG_ROWS;
+        slabFloats = std::max(slabFloats, (tx * q.M + ty * q.N) * q.K);
+        lossSlots = std::max(lossSlots, (int)(tx * ty));
+    }
+    for (auto& o : order)
+        std::stable_sort(o.begin(), o.end(), [&](int x, int y) { return items[x].M * items[x].N * items[x].K > items[y].M * items[y].N * items[y].K; });
+    int slots[2] = {0, 0};
+    rc = batch_slots<8>(cus, &slots[0]);
+    if (rc == PMX_OK) rc = batch_slots<16>(cus, &slots[1]);
+    if (rc != PMX_OK) return rc;
+    int maxSlots = 1;
+    for (int k = 0; k < 2; ++k) {
+        if (p->max_workgroups > 0 && slots[k] > p->max_workgroups) slots[k] = p->max_workgroups;
+        if ((size_t)slots[k] > order[k].size()) slots[k] = (int)order[k].size();
+        maxSlots = std::max(maxSlots, slots[k]);
+    }
+    // S in the kernels' orientation
+    std::vector<float> hSt((size_t)nS);
+    for (int64_t b = 0; b < B; ++b) {
+        const pmx_batch_item& q = items[b];
+        const float* s = S + q.offS;
+        float* d = hSt.data() + q.offS;
+        for (int64_t n = 0; n < q.N; ++n)
+            for (int k = 0; k < q.K; ++k) d[n * q.K + k] = s[(int64_t)k * q.N + n];
+    }
+    // the Nesterov sequence (utils.py:198-206) as pmx_pgm_begin / next_omega step through it
+    std::vector<float> omega;
+    if (p->accelerated) {
+        omega.resize((size_t)std::max(p->max_iter, 1));
+        double t = 0.5 * (1.0 + sqrt(5.0));            // the first omega (== 0) is consumed at it = 0
+        for (int it = 0; it < p->max_iter; ++it) {
+            const double t1 = 0.5 * (1.0 + sqrt(4.0 * t * t + 1.0));
+            omega[it] = (float)((t - 1.0) / t1);
+            t = t1;
+        }
+    }
+    BatchBufs bufs;
+    BatchArgs a{};
+    pmx_batch_item* dItems;
+    int* dOrder;
+    float* dY;
+    float* dOmega = nullptr;
+    rc = bufs.get(&dItems, (size_t)B);
+    if (rc == PMX_OK) rc = bufs.get(&dOrder, (size_t)B);
+    if (rc == PMX_OK) rc = bufs.get(&a.counter, 4);
+    if (rc == PMX_OK) rc = bufs.get(&dY, (size_t)nY);
+    if (rc == PMX_OK) rc = bufs.get(&a.X[0], (size_t)nA);
+    if (rc == PMX_OK) rc = bufs.get(&a.X[1], (size_t)nS);
+    if (rc == PMX_OK && p->accelerated) rc = bufs.get(&a.Xe[0], (size_t)nA);
+    if (rc == PMX_OK && p->accelerated) rc = bufs.get(&a.Xe[1], (size_t)nS);
+    if (rc == PMX_OK && p->accelerated) rc = bufs.get(&dOmega, omega.size());
+    if (rc == PMX_OK) rc = bufs.get(&a.status, (size_t)B);
+    if (rc == PMX_OK) rc = bufs.get(&a.out, (size_t)B);
+    if (rc == PMX_OK) rc = bufs.get(&a.slabs, (size_t)maxSlots * slabFloats);
+    if (rc == PMX_OK) rc = bufs.get(&a.eigG, (size_t)maxSlots * 2 * BATCH_KP * BATCH_KP);
+    if (rc == PMX_OK) rc = bufs.get(&a.eigQ, (size_t)maxSlots * 2 * BATCH_KP * BATCH_KP);
+    if (rc == PMX_OK) rc = bufs.get(&a.lossPart, (size_t)maxSlots * lossSlots);
+    if (rc != PMX_OK) return rc;
+    HIP_CHECK(hipEventCreate(&bufs.ev[0]));
+    HIP_CHECK(hipEventCreate(&bufs.ev[1]));
+    HIP_CHECK(hipMemcpy(dItems, items, (size_t)B * sizeof(pmx_batch_item), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dOrder, order[0].data(), order[0].size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dOrder + order[0].size(), order[1].data(), order[1].size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemset(a.counter, 0, 4 * sizeof(unsigned)));
+    HIP_CHECK(hipMemcpy(dY, Y, (size_t)nY * sizeof(float), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(a.X[0], A, (size_t)nA * sizeof(float), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(a.X[1], hSt.data(), (size_t)nS * sizeof(float), hipMemcpyHostToDevice));
+    if (p->accelerated) {                    // omega = 0 on the first read: the first extrapolated point is X itself
+        HIP_CHECK(hipMemcpy(a.Xe[0], a.X[0], (size_t)nA * sizeof(float), hipMemcpyDeviceToDevice));
+        HIP_CHECK(hipMemcpy(a.Xe[1], a.X[1], (size_t)nS * sizeof(float), hipMemcpyDeviceToDevice));
+        HIP_CHECK(hipMemcpy(dOmega, omega.data(), omega.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    HIP_CHECK(hipMemset(a.out, 0, (size_t)B * sizeof(pmx_batch_result)));
+    a.items = dItems;
+    a.Y = dY;
+    a.slabFloats = slabFloats;
+    a.lossSlots = lossSlots;
+    a.omega = dOmega;
+    for (int j = 0; j < 2; ++j) {
+        a.prox[j] = to_dev(p->prox[j], nullptr);
+        a.e_rel[j] = p->e_rel[j];
+        a.fixed[j] = p->fixed_steps[j];
+    }
+    a.scale = (double)(float)p->step_scale;     // (pmx_pgm_params::step_scale is a float: the single call's number)
+    a.use_fixed = p->use_fixed_steps != 0;
+    a.accelerated = p->accelerated != 0;
+    a.max_iter = p->max_iter;
+    unsigned* counters = a.counter;
+    HIP_CHECK(hipEventRecord(bufs.ev[0], nullptr));
+    for (int k = 0; k < 2; ++k) {
+        if (order[k].empty()) continue;
+        a.order = dOrder + (k ? order[0].size() : 0);
+        a.n = (int)order[k].size();
+        a.counter = counters + k;
+        if (k == 0) hipLaunchKernelGGL(k_batch_pgm<8>, dim3(slots[k]), dim3(256), 0, nullptr, a);
+        else hipLaunchKernelGGL(k_batch_pgm<16>, dim3(slots[k]), dim3(256), 0, nullptr, a);
+        HIP_CHECK(hipGetLastError());
+    }
+    HIP_CHECK(hipEventRecord(bufs.ev[1], nullptr));
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+    float ms = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms, bufs.ev[0], bufs.ev[1]));
+    // results first, the factors last: the caller's arrays change only when everything has succeeded
+    std::vector<float> hA((size_t)nA);
+    HIP_CHECK(hipMemcpy(out, a.out, (size_t)B * sizeof(pmx_batch_result), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(hA.data(), a.X[0], (size_t)nA * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(hSt.data(), a.X[1], (size_t)nS * sizeof(float), hipMemcpyDeviceToHost));
+    for (int64_t b = 0; b < B; ++b) {
+        const pmx_batch_item& q = items[b];
+        memcpy(A + q.offA, hA.data() + q.offA, (size_t)(q.M * q.K) * sizeof(float));
+        const float* s = hSt.data() + q.offS;
+        float* d = S + q.offS;
+        for (int64_t n = 0; n < q.N; ++n)
+            for (int k = 0; k < q.K; ++k) d[(int64_t)k * q.N + n] = s[n * q.K + k];
+    }
+    g_batch_launch_ms = ms;
+    return PMX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -285,6 +285,24 @@ def _nmf_sharded(Y, A, S, W, prox_A, prox_S, algorithm, step, max_iter, e_rel, c
     return conv
 
 
+def nmf_batch(Ys, As, Ss, prox_A=operators.prox_plus, prox_S=operators.prox_plus, step=None, accelerated=False, max_iter=1000, e_rel=1e-3,
+              max_workgroups=0):
+    """B small factorisations in ONE launch: problem b gets exactly what `nmf(Ys[b], As[b], Ss[b], prox_A=, prox_S=, step=, accelerated=,
+    max_iter=, e_rel=)` does with algorithm=pgm -- the same bits --, each stopping on its own test (algorithms.py:130-135) or at max_iter.
+
+    Ys, As, Ss: sequences of equal length of 2-D float32 host arrays, M_b x N_b, M_b x K_b and K_b x N_b (shapes may differ from problem
+    to problem; three 3-D arrays are sequences of views); every As[b] and Ss[b] is updated in place, whatever its strides.  Each problem
+    is a small one: K <= 16, M <= 4096, N <= 8192, M N <= 2^20 (ValueError otherwise, as for shapes that do not fit together).
+    prox_A, prox_S: common to the batch, this library's operators that act within a row with scalar parameters (prox_id .. prox_soft_plus,
+    prox_unity* along the short axis -- axis=1 on A, axis=0 on S --, AlternatingProjections of these).  step: None / nmf.step_pgm (the
+    Lipschitz rule), nmf.scaled_step_pgm(c) or nmf.constant_step(a, b).  NotImplementedError for everything else the single call takes:
+    float64, arrays on a GPU, user callables, Barzilai-Borwein, prox_max_entropy, per-component parameters, long-axis prox_unity* --
+    loop over nmf() for those.  max_workgroups > 0 caps the grid (tests).
+    -> batch.BatchResult: converged (B, 2), iterations (B,), steps (B, 2)."""
+    from . import batch
+    return batch.run(Ys, As, Ss, prox_A, prox_S, step, accelerated, max_iter, e_rel, max_workgroups=max_workgroups)
+
+
 def nmf(
     Y,
     A,
