@@ -512,6 +512,9 @@ int pmx_chain_status(pmx_ctx* ctx, int* halted, int* reason, int* it_done, int l
 /* resume an iteration that ran out of sub-iteration passes: passes t0 .. t0+n-1, then finish+decide */
 int pmx_adaprox_more_subs(pmx_ctx* ctx, int t0, int n);
 int pmx_iter_result(pmx_ctx* ctx, pmx_result* res);
+/* synchronise and report the sums of the last outer / Boyd test of each block: norms[2 j] = sum (X_j_new - X_j_old)^2,
+ * norms[2 j + 1] = sum X_j_new^2 (DevStatus::norms; what the tests compare with the oracle's) */
+int pmx_iter_norms(pmx_ctx* ctx, double norms[4]);
 
 /* ---- the collectives themselves, for a caller without torch.distributed -------------------------------------------------
  * No reference counterpart (the reference is single-process).  The phase protocol above leaves its one all-reduce -- or, with

@@ -386,14 +386,24 @@ def _l2(x):
 
 
 def bsdmm_nmf(Y, A, S, prox_A=("plus",), prox_S=("plus",), proxs_g=None, max_iter=1000,
-              e_rel=1e-3, e_abs=0, callback=None, trace=None, state=None):
+              e_rel=1e-3, e_abs=0, callback=None, trace=None, state=None, grad=None, step=None, update_order=None, log=None):
     """`nmf(Y, A, S, algorithm=bsdmm, proxs_g=...)` (nmf.py:178-203 -> algorithms.py:653-850)
     for the only configuration nmf() can reach without crashing: step=None, Ls=None (identity
     adapters, spectral norm 1: utils.py:56-59,70-74), steps_g_update="steps_f".
 
     proxs_g: None, or [gA, gS] where each entry is None or a list of prox specs.
     Returns (converged(list of 2 bools), n_iter).  If `state` is a dict it receives the final
-    Z and U lists (lost by the reference) for kernel-level comparisons."""
+    Z and U lists (lost by the reference) for kernel-level comparisons; it holds them (the live arrays) from the first
+    iteration on, so a `callback` can read the Z and U that go with the A and S it is handed.
+    `grad`: None -> the NMF likelihood gradient of Y; or a callable (A, S) -> (gA, gS) evaluated at the current factors
+    before each block update (Y may then be None), as in pgm_nmf.
+    `step`: None -> nmf.step_pgm at the current factors; or a callable (it, j) -> step_f of block j (the reference's
+    steps_f_cb, algorithms.py:807), cast to the factors' dtype.
+    `update_order`: None -> (0, 1); else the blocks in the order given (algorithms.py:730-736, :805).  A block that is
+    never updated keeps the reference's initial None in `converged` (:793).
+    `log`: a list that receives ("g", it, j, i, lR, lS, e_pri, e_dual) for every Boyd decision (i = 0 for a block
+    without constraints) and ("b", it, j, d2, x2, conv) for every block update: d2 = sum (X_new - X_old)^2 and
+    x2 = sum X_new^2 in the factors' dtype."""
     X = [A, S]
     specs_f = [prox_A, prox_S]
     if proxs_g is None:
@@ -411,14 +421,19 @@ def bsdmm_nmf(Y, A, S, prox_A=("plus",), prox_S=("plus",), proxs_g=None, max_ite
     while it < max_iter:                                               # algorithms.py:800
         if trace is not None:
             trace.append((A.copy(), S.copy()))
+        if state is not None:
+            state["Z"], state["U"] = Z, U
         if callback is not None:
             callback(A, S, it=it)                                      # no StopIteration handler (:802)
-        for j in range(2):                                             # Gauss-Seidel (:805)
-            sf = lipschitz_steps(X[0], X[1])[j]                        # nmf.py:187-193, slack == 1
-            Gj = residual_gradients(X[0], X[1], Y)[j]                  # nmf.py:181-185 (current Xs)
+        for j in ((0, 1) if update_order is None else update_order):   # Gauss-Seidel (:805)
+            if step is None:
+                sf = lipschitz_steps(X[0], X[1])[j]                    # nmf.py:187-193, slack == 1
+            else:
+                sf = X[j].dtype.type(step(it, j))                      # steps_f_cb (:807)
+            Gj = residual_gradients(X[0], X[1], Y)[j] if grad is None else grad(X[0], X[1])[j]   # nmf.py:181-185 (current Xs)
             n_el = X[j].size
+            old = X[j].copy() if (log is not None or proxs_g[j] is None) else None
             if proxs_g[j] is None:                                     # utils.py:319-327
-                old = X[j].copy()
                 X[j][:] = apply_prox(X[j] - sf * Gj, sf, specs_f[j])
                 Z[j][:] = X[j]
                 lR = 0.0
@@ -427,6 +442,8 @@ def bsdmm_nmf(Y, A, S, prox_A=("plus",), prox_S=("plus",), proxs_g=None, max_ite
                 e_pri = math.sqrt(Z[j].size) * ea[j] + er[j] * max(_l2(X[j]), _l2(Z[j]))
                 e_dual = math.sqrt(n_el) * ea[j] + er[j] * _l2(U[j])
                 conv[j] = (lR <= e_pri) and (lS <= e_dual)
+                if log is not None:
+                    log.append(("g", it, j, 0, lR, lS, e_pri, e_dual))
             else:
                 sg = [sf * 1 * nblk * ncon[j]] * ncon[j]               # get_step_g, utils.py:269-279
                 dX = np.sum([sf / sg[i] * (X[j] - Z[j][i] + U[j][i]) for i in range(ncon[j])], axis=0)  # utils.py:330-336
@@ -441,13 +458,17 @@ def bsdmm_nmf(Y, A, S, prox_A=("plus",), prox_S=("plus",), proxs_g=None, max_ite
                     e_pri = math.sqrt(Z[j][i].size) * ea[j] + er[j] * max(_l2(X[j]), _l2(Z[j][i]))
                     e_dual = math.sqrt(n_el) * ea[j] + er[j] * _l2(U[j][i] / sg[i])
                     ok &= (_l2(R) <= e_pri) and (_l2(Sd) <= e_dual)    # utils.py:386-390
+                    if log is not None:
+                        log.append(("g", it, j, i, _l2(R), _l2(Sd), e_pri, e_dual))
                 conv[j] = bool(ok)
+            if log is not None:
+                log.append(("b", it, j, _sumsq(X[j] - old), _sumsq(X[j]), bool(conv[j])))
         it += 1
         if all(conv):
             break
     if state is not None:
         state["Z"], state["U"] = Z, U
-    return [bool(c) for c in conv], it
+    return [None if (c is None and update_order is not None) else bool(c) for c in conv], it
 
 
 # --------------------------------------------------------------------------------------

@@ -135,6 +135,7 @@ _SIGNATURES = {
     "pmx_chain_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pmx_adaprox_more_subs": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pmx_iter_result": (C.c_int, [C.c_void_p, C.POINTER(Result)]),
+    "pmx_iter_norms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "pmx_set_host_grad": (C.c_int, [C.c_void_p, C.c_int]),
     "pmx_set_s_split": (C.c_int, [C.c_void_p, C.c_int]),
     "pmx_comm_layout_split": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -4177,6 +4177,14 @@ extern "C" int pmx_iter_result(pmx_ctx* c, pmx_result* res) {
     return PMX_OK;
 }
 
+extern "C" int pmx_iter_norms(pmx_ctx* c, double norms[4]) {
+    if (!c || !norms) FAIL(PMX_E_INVALID, "NULL argument");
+    int rc = read_status(c);
+    if (rc != PMX_OK) return rc;
+    for (int j = 0; j < 2; ++j) { norms[2 * j] = c->hstatus->norms[j][0]; norms[2 * j + 1] = c->hstatus->norms[j][1]; }
+    return PMX_OK;
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Collectives through the C ABI (missing 7): the row-sharded protocol (pmx_*_phase) leaves its one

@@ -749,6 +749,12 @@ class DeviceNMF:
         _lib.check(self.lib.pmx_bsdmm_run(self.h, int(n_iter), C.byref(r)))
         return r
 
+    def iter_norms(self):
+        """((d2_A, x2_A), (d2_S, x2_S)): the sums of each block's last outer / Boyd test (include/pmx.h: pmx_iter_norms)."""
+        v = (C.c_double * 4)()
+        _lib.check(self.lib.pmx_iter_norms(self.h, v))
+        return (v[0], v[1]), (v[2], v[3])
+
 
 def open_weighted(M, N, K, W, **kw):
     """Context for a weighted likelihood: the default arithmetic mode where its kernel takes weights, exact fp32
